@@ -23,14 +23,22 @@ absolute throughput numbers => vs_baseline = null.
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for
 N > 1 the driver launches it under torch.distributed.run with one rank per
 GPU. Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: set up, warm up,
+time the K steps, print the line. `--dump-outputs DIR` additionally writes
+what the last timed step computed as DIR/<name>.npy (see dump_outputs), for
+comparing two builds output for output. Secondary measurements belong
+behind `--full` (off by default); there are none yet.
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import random
 import time
+import warnings
 
 import torch
 
@@ -82,12 +90,84 @@ def synth_preds(model_idxs, N, C, device, seed_base=1234,
     return out, labels
 
 
+def dump_outputs(out_dir, last, selector, write=True):
+    """Write what the timed path computed in its last step as .npy files.
+
+    selected_index / selected_score / best_model are the three values one
+    step hands its caller; pbest (H,) is the P(best) vector best_model is
+    the argmax of and pi_hat (C,) the class marginal behind it;
+    trajectory_index / trajectory_score hold every step's selection since
+    the selector was built (warmup included). Integers are stored as
+    float64 (exact far beyond any pool size), the rest as computed (fp32).
+    All of it is a few KB at any config. Inputs and tie-breaks are seeded
+    and the selector is built reproducibly (see reproducible_setup), so
+    equal arguments give bit-equal files from run to run.
+    """
+    import numpy as np
+
+    idx, q, best = last
+    pbest = selector.get_pbest()
+    if not write:
+        return
+    arrays = {
+        "selected_index": np.array([int(idx)], np.float64),
+        "selected_score": np.array([float(q)], np.float64),
+        "best_model": np.array([int(best)], np.float64),
+        "pbest": pbest.detach().float().cpu().numpy(),
+        "pi_hat": selector.pi_hat.detach().float().cpu().numpy(),
+        "trajectory_index": np.array(selector.labeled_idxs, np.float64),
+        "trajectory_score": np.array([float(v) for v in selector.q_vals],
+                                     np.float64),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
+@contextlib.contextmanager
+def reproducible_setup():
+    """Build the selector with torch's deterministic algorithms.
+
+    The consensus confusion prior is a float index_add_ over the pool,
+    which on GPU sums with atomics in whatever order the blocks arrive.
+    The resulting last-bit differences in the Dirichlet prior matter: at
+    the headline config the EIG maximum sits on the fp32 cancellation
+    floor of H_before and hundreds of candidates tie for it, so two runs
+    picked different points from the second step on. With the
+    deterministic (sorted) accumulation the prior, and every step after
+    it, is bit-identical from run to run (checked over checksums of the
+    selector state on MI355X). Only the one-time setup is affected; the
+    per-step path has no such op (its kernels reduce in a fixed order)
+    and runs with the caller's settings.
+    """
+    was = torch.are_deterministic_algorithms_enabled()
+    warn_only = torch.is_deterministic_algorithms_warn_only_enabled()
+    torch.use_deterministic_algorithms(True, warn_only=True)
+    try:
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            yield
+    finally:
+        torch.use_deterministic_algorithms(was, warn_only=warn_only)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=800)
     ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step returned to its caller (and the posterior "
+                         "behind it) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement; a plain "
+                         "run only sets up, warms up, times the steps and "
+                         "prints the result line (this benchmark has no "
+                         "secondary measurement yet, so --full adds none)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     comm = init_from_env() if world > 1 else get_comm()
@@ -123,14 +203,16 @@ def main():
 
     random.seed(0)
     torch.manual_seed(0)
-    selector = CODA(ds, comm=comm, prefilter_n=PREFILTER_N,
-                    chunk_size=CHUNK)
+    with reproducible_setup():
+        selector = CODA(ds, comm=comm, prefilter_n=PREFILTER_N,
+                        chunk_size=CHUNK)
 
     def one_step():
         idx, q = selector.get_next_item_to_label()
         y = oracle(int(idx))
         selector.add_label(idx, y, q)
-        selector.get_best_model_prediction()
+        best = selector.get_best_model_prediction()
+        return idx, q, best
 
     def sync():
         comm.barrier()
@@ -142,9 +224,13 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        one_step()
+        last = one_step()
     sync()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs:
+        # get_pbest may run collectives: every rank calls, rank 0 writes
+        dump_outputs(args.dump_outputs, last, selector, comm.rank == 0)
 
     # MAX over ranks
     et = torch.tensor([elapsed], device=device if device.type == "cuda"

@@ -256,3 +256,51 @@ def test_bench_rejects_gpu_count_mismatch():
                        timeout=120)
     assert r.returncode != 0
     assert "WORLD_SIZE" in (r.stdout + r.stderr)
+
+
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's results as float .npy
+    files; equal arguments give equal files (seeded inputs), --steps sets
+    the number of timed steps, and --full is accepted."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    env.update(CODA_BENCH_H="6", CODA_BENCH_N="150", CODA_BENCH_C="4",
+               CODA_BENCH_CHUNK="32", CUDA_VISIBLE_DEVICES="",
+               HIP_VISIBLE_DEVICES="")
+
+    def run(out, *extra):
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1",
+                            "--steps", "3", "--warmup", "2",
+                            "--dump-outputs", str(out), *extra],
+                           cwd=repo, env=env, capture_output=True, text=True,
+                           timeout=300)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        d = json.loads([l for l in r.stdout.splitlines()
+                        if l.startswith("{")][-1])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        assert abs(d["value"] * d["ms_per_step"] - 1000.0) < 1e-6 * 1000
+        return {f[:-4]: np.load(os.path.join(out, f))
+                for f in sorted(os.listdir(out))}
+
+    a = run(tmp_path / "a")
+    b = run(tmp_path / "b", "--full")
+    assert set(a) == {"selected_index", "selected_score", "best_model",
+                      "pbest", "pi_hat", "trajectory_index",
+                      "trajectory_score"}
+    assert set(a) == set(b)
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64), name
+        np.testing.assert_array_equal(a[name], b[name], err_msg=name)
+    assert a["pbest"].shape == (6,) and a["pi_hat"].shape == (4,)
+    assert abs(float(a["pbest"].sum()) - 1.0) < 1e-3
+    assert abs(float(a["pi_hat"].sum()) - 1.0) < 1e-3
+    # warmup + timed selections, the last of which is the dumped step
+    assert a["trajectory_index"].shape == (5,)
+    assert a["trajectory_index"][-1] == a["selected_index"][0]
+    assert int(a["best_model"][0]) == int(a["pbest"].argmax())

@@ -1,4 +1,4 @@
-"""Paper-protocol-length trajectory parity vs the mounted reference.
+"""Paper-protocol-length trajectory parity vs the upstream reference.
 
 Extends tests/test_reference_parity.py from 5-step smoke parity to
 100-step trajectories (the reference experiment length, main.py:35) on
@@ -16,53 +16,45 @@ choice (teacher forcing), so the dynamics stay comparable for the full
 100 steps. Methods whose selection involves no fp comparison (IID) are
 held to exact selection equality.
 
-Runs only where /root/reference is mounted (dev container); the
-reference engine is the slow side (~1 s/step at C=126 on CPU).
+The reference side is replayed from recordings under
+tests/golden/reference_parity/ (made by oracle/record_parity_golden.py
+from a checkout of the reference, which ran along its own seeded
+selections exactly as described above), so the tests need nothing
+outside the repository.
 """
-import contextlib
-import io
 import os
 import random
-import sys
 
+import numpy as np
 import pytest
 import torch
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(
-    not os.path.isdir(os.path.join(REF, "coda")),
-    reason="reference tree not mounted")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                      "golden", "reference_parity")
 
 
-@pytest.fixture(scope="module")
-def refpkg():
-    sys.path.insert(0, REF)
-    try:
-        import coda.coda as ref_coda
-        import coda.baselines.iid as ref_iid
-        import coda.baselines.uncertainty as ref_unc
-        import coda.baselines.activetesting as ref_at
-        import coda.baselines.vma as ref_vma
-        import coda.baselines.modelpicker as ref_mp
-        from coda.options import LOSS_FNS as REF_LOSS
-        yield dict(coda=ref_coda, iid=ref_iid, unc=ref_unc, at=ref_at,
-                   vma=ref_vma, mp=ref_mp, loss=REF_LOSS)
-    finally:
-        sys.path.remove(REF)
+def _golden(name, H, N, C, seed):
+    """Load a recording, checking it was made on this very task."""
+    g = np.load(os.path.join(GOLDEN, name + ".npz"))
+    assert g["task"].tolist() == [H, N, C, seed], \
+        f"{name}: recorded on task {g['task'].tolist()}, re-record"
+    return g
 
 
-class _RefDS:
-    pass
+def _eig_steps(g):
+    """Per-step (EIG vector, candidate list) of a recorded CODA run."""
+    off = 0
+    for n in g["lens"].tolist():
+        yield (torch.from_numpy(g["q_flat"][off:off + n]),
+               g["cand_flat"][off:off + n].tolist())
+        off += n
 
 
 def _task(H, N, C, seed):
     from coda_amd.datasets import make_synthetic_task
     preds, labels = make_synthetic_task(H=H, N=N, C=C, seed=seed)
-    rds = _RefDS()
-    rds.preds, rds.labels = preds.clone(), labels.clone()
-    rds.device = torch.device("cpu")
     from coda_amd.datasets import Dataset
-    return rds, Dataset.from_tensors(preds, labels, "cpu"), labels
+    return Dataset.from_tensors(preds, labels, "cpu"), labels
 
 
 def _ref_select(q_vals, candidates, seed):
@@ -84,18 +76,16 @@ def _ref_select(q_vals, candidates, seed):
     (6, 400, 2, 100),     # binary edge (glue/camelyon group)
     (10, 120, 126, 100),  # DomainNet-126 class-count edge
 ])
-def test_coda_100step_trajectory_parity(refpkg, H, N, C, steps):
+def test_coda_100step_trajectory_parity(H, N, C, steps):
     from coda_amd import CODA
 
-    rds, ds, labels = _task(H, N, C, seed=H + C)
-    random.seed(0); torch.manual_seed(0)
-    ref = refpkg["coda"].CODA(rds)
+    ref = _golden(f"coda_100step_{H}_{N}_{C}", H, N, C, H + C)
+    assert len(ref["lens"]) == steps
+    ds, labels = _task(H, N, C, seed=H + C)
     random.seed(0); torch.manual_seed(0)
     mine = CODA(ds)
 
-    for m in range(steps):
-        with contextlib.redirect_stderr(io.StringIO()):
-            q_r, cand_r = ref.eig_batched()
+    for m, (q_r, cand_r) in enumerate(_eig_steps(ref)):
         q_m, cand_m = mine.eig_batched()
         assert list(cand_r) == list(cand_m), m
         # EIG parity: EIG = H_before - (candidate sum) is a
@@ -107,40 +97,38 @@ def test_coda_100step_trajectory_parity(refpkg, H, N, C, steps):
         # advance both along the reference's own (seeded) selection
         idx, q = _ref_select(q_r, cand_r, seed=1000 + m)
         y = int(labels[idx])
-        ref.add_label(idx, y, q)
         mine.add_label(idx, y, q)
         if (m + 1) % 10 == 0:
-            torch.testing.assert_close(mine.get_pbest().reshape(-1),
-                                       ref.get_pbest().reshape(-1),
-                                       rtol=1e-3, atol=1e-6)
+            torch.testing.assert_close(
+                mine.get_pbest().reshape(-1),
+                torch.from_numpy(ref["pbest"][(m + 1) // 10 - 1]),
+                rtol=1e-3, atol=1e-6)
 
 
 @pytest.mark.timeout(600)
-def test_iid_100step_exact(refpkg):
+def test_iid_100step_exact():
     """IID selection is pure seeded RNG over the same list - exact."""
     from coda_amd.baselines import IID
     from coda_amd.options import LOSS_FNS
 
-    rds, ds, labels = _task(H=7, N=250, C=6, seed=21)
-    ref = refpkg["iid"].IID(rds, refpkg["loss"]["acc"])
+    ref = _golden("iid_100step", 7, 250, 6, 21)
+    ds, labels = _task(H=7, N=250, C=6, seed=21)
     mine = IID(ds, LOSS_FNS["acc"])
     for m in range(100):
-        random.seed(1000 + m)
-        ir, qr = ref.get_next_item_to_label()
+        ir, qr = int(ref["idx"][m]), float(ref["q"][m])
         random.seed(1000 + m)
         im, qm = mine.get_next_item_to_label()
-        assert int(ir) == int(im) and abs(qr - qm) < 1e-9
-        y = int(labels[int(ir)])
-        ref.add_label(int(ir), y, qr)
+        assert ir == int(im) and abs(qr - qm) < 1e-9
+        y = int(labels[ir])
         mine.add_label(int(im), y, qm)
         torch.testing.assert_close(mine.get_risk_estimates(),
-                                   ref.get_risk_estimates())
+                                   torch.from_numpy(ref["risk"][m]))
 
 
 @pytest.mark.timeout(900)
 @pytest.mark.parametrize("method", ["uncertainty", "activetesting",
                                     "vma", "model_picker"])
-def test_baseline_100step_trajectory_parity(refpkg, method):
+def test_baseline_100step_trajectory_parity(method):
     """AT/VMA: same seeded stochastic draws (identical acquisition
     distributions); risk estimates compared as vectors each step (their
     best-model argmin has exact ties early on, where either pick is
@@ -150,40 +138,35 @@ def test_baseline_100step_trajectory_parity(refpkg, method):
                                     ModelPicker)
     from coda_amd.options import LOSS_FNS
 
-    rds, ds, labels = _task(H=7, N=250, C=6, seed=21)
+    ref = _golden(f"baseline_100step_{method}", 7, 250, 6, 21)
+    ds, labels = _task(H=7, N=250, C=6, seed=21)
     if method == "uncertainty":
-        ref = refpkg["unc"].Uncertainty(rds, refpkg["loss"]["acc"])
         mine = Uncertainty(ds, LOSS_FNS["acc"])
     elif method == "activetesting":
-        ref = refpkg["at"].ActiveTesting(rds, refpkg["loss"]["acc"])
         mine = ActiveTesting(ds, LOSS_FNS["acc"])
     elif method == "vma":
-        ref = refpkg["vma"].VMA(rds, refpkg["loss"]["acc"])
         mine = VMA(ds, LOSS_FNS["acc"])
     else:
-        ref = refpkg["mp"].ModelPicker(rds, epsilon=0.38)
         mine = ModelPicker(ds, epsilon=0.38)
 
     flips = 0
     for m in range(100):
-        random.seed(1000 + m); torch.manual_seed(1000 + m)
-        with contextlib.redirect_stderr(io.StringIO()):
-            ir, qr = ref.get_next_item_to_label()
+        ir, qr = int(ref["idx"][m]), float(ref["q"][m])
         random.seed(1000 + m); torch.manual_seed(1000 + m)
         im, qm = mine.get_next_item_to_label()
-        if int(ir) != int(im):
+        if ir != int(im):
             # deterministic argmin/argmax near-tie: both engines must
             # consider the two picks equivalent
             flips += 1
             assert abs(qr - qm) < 1e-4 * max(1.0, abs(qr)), (m, qr, qm)
-        y = int(labels[int(ir)])
-        ref.add_label(int(ir), y, qr)
-        mine.add_label(int(ir), y, qr)      # teacher-force ref's pick
+        y = int(labels[ir])
+        mine.add_label(ir, y, qr)           # teacher-force ref's pick
         if method == "model_picker":
-            torch.testing.assert_close(mine.posterior, ref.posterior,
+            torch.testing.assert_close(mine.posterior,
+                                       torch.from_numpy(ref["state"][m]),
                                        rtol=1e-5, atol=1e-7)
         elif method in ("activetesting", "vma"):
-            r_risk, _ = ref.get_lure_risks_and_vars()
+            r_risk = torch.from_numpy(ref["state"][m])
             m_risk, _ = mine.get_lure_risks_and_vars()
             torch.testing.assert_close(m_risk, r_risk, rtol=1e-4,
                                        atol=1e-6)
@@ -194,31 +177,28 @@ def test_baseline_100step_trajectory_parity(refpkg, method):
 
 
 @pytest.mark.timeout(600)
-def test_coda_hyperparameter_grid_parity(refpkg):
+def test_coda_hyperparameter_grid_parity():
     """Non-default hyperparameters (lr, alpha, multiplier) track the
     reference for 25 steps each."""
     from coda_amd import CODA
 
-    for kwargs in ({"learning_rate": 0.1},
-                   {"alpha": 0.5},
-                   {"multiplier": 1.0},
-                   {"learning_rate": 0.05, "alpha": 0.8,
-                    "multiplier": 4.0}):
-        rds, ds, labels = _task(H=6, N=200, C=4, seed=33)
-        random.seed(0); torch.manual_seed(0)
-        ref = refpkg["coda"].CODA(rds, **kwargs)
+    for i, kwargs in enumerate(({"learning_rate": 0.1},
+                                {"alpha": 0.5},
+                                {"multiplier": 1.0},
+                                {"learning_rate": 0.05, "alpha": 0.8,
+                                 "multiplier": 4.0})):
+        ref = _golden(f"coda_hyper_{i}", 6, 200, 4, 33)
+        assert len(ref["lens"]) == 25
+        ds, labels = _task(H=6, N=200, C=4, seed=33)
         random.seed(0); torch.manual_seed(0)
         mine = CODA(ds, **kwargs)
-        for m in range(25):
-            with contextlib.redirect_stderr(io.StringIO()):
-                q_r, cand_r = ref.eig_batched()
+        for m, (q_r, cand_r) in enumerate(_eig_steps(ref)):
             q_m, cand_m = mine.eig_batched()
             assert list(cand_r) == list(cand_m)
             torch.testing.assert_close(q_m, q_r, rtol=1e-3, atol=2e-6)
             idx, q = _ref_select(q_r, cand_r, seed=500 + m)
             y = int(labels[idx])
-            ref.add_label(idx, y, q)
             mine.add_label(idx, y, q)
         torch.testing.assert_close(mine.get_pbest().reshape(-1),
-                                   ref.get_pbest().reshape(-1),
+                                   torch.from_numpy(ref["pbest"][0]),
                                    rtol=1e-3, atol=1e-6)

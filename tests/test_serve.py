@@ -78,7 +78,7 @@ def test_synthetic_builder(tmp_path):
          "--synthetic", "4", "--n", "60", "--classes-n", "5",
          "--out", str(out)],
         capture_output=True, text=True, timeout=120,
-        cwd="/root/repo")
+        cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     assert r.returncode == 0, r.stderr
     t = torch.load(str(out), weights_only=True)
     assert t.shape == (4, 60, 5)
