@@ -11,16 +11,20 @@
 //                          (K, P). The baseline curve exp2(s_base)*w is
 //                          folded into the B operand (egw).
 //
-//   pair_gemm_entropy{16,64}_kernel
-//                          one workgroup per class-uniform pair tile:
-//                          bf16 MFMA (tile x 2H x P) pairing GEMM with
-//                          the variant-select + normalize + log2
-//                          entropy epilogue fused (the (K, 2H) M tensor
-//                          never reaches global memory). The 64-pair
-//                          variant (2H <= 512) stages both operands in
-//                          LDS, quartering the dominant B traffic vs
-//                          the 16-pair tile; the 16-pair variant covers
-//                          H up to 1024.
+//   pair_gemm_entropy{16,128}_kernel
+//                          one workgroup per class-uniform pair tile
+//                          (or group of same-class tiles): bf16 MFMA
+//                          (tile x 2H x P) pairing GEMM with the
+//                          variant-select + normalize + log2 entropy
+//                          epilogue fused (the (K, 2H) M tensor never
+//                          reaches global memory). The 128-pair
+//                          variant (2H <= 272, i.e. H <= 136) keeps the
+//                          class's whole B operand resident in LDS,
+//                          dividing the dominant B traffic by 8 vs the
+//                          16-pair tile; the 16-pair variant covers H
+//                          up to 1024. 128-pair tiles with 2H > 272
+//                          take the split wide pipeline below (M
+//                          written to global as bf16, H <= 2048).
 //
 //   pair_eig_finalize_kernel
 //                          one wave per candidate: EIG[b] = H_before -
@@ -418,7 +422,7 @@ pair_gemm_entropy128_kernel(const hip_bfloat16* __restrict__ a16,
 }
 
 // ---------------------------------------------------------------------
-// Wide-H pipeline (288 < 2H <= 4096, i.e. the multi-GPU H=256..1024
+// Wide-H pipeline (272 < 2H <= 4096, i.e. the multi-GPU H=256..1024
 // pools): the fused B-resident tile cannot hold egw[c] or the M tile in
 // LDS, so the pairing GEMM writes M (K, 2H) bf16 to global with a
 // standard 128x128 double-buffered MFMA tile (B traffic divided by 128
@@ -898,7 +902,7 @@ torch::Tensor pair_gemm_entropy(torch::Tensor a16, torch::Tensor egw,
             launch(pairops::pair_gemm_entropy128_kernel<16>);
         else launch(pairops::pair_gemm_entropy128_kernel<17>);
     } else {
-        TORCH_CHECK(tile == 16, "tile must be 16 or 64");
+        TORCH_CHECK(tile == 16, "tile must be 16 or 128");
         const size_t shmem = 16 * P_POINTS * sizeof(hip_bfloat16)
                            + (size_t)16 * mstride * sizeof(float);
         TORCH_CHECK(shmem <= 160 * 1024, "H too large for the fused "

@@ -51,7 +51,7 @@ def tile_for(H: int, B: int) -> int:
     """MFMA tile height (pairs per class-uniform tile).
 
     128-pair tiles divide the dominant GEMM B traffic by 8 vs 16-pair
-    tiles (H <= 144: B resident in LDS, fused epilogue; larger H: the
+    tiles (H <= 136: B resident in LDS, fused epilogue; larger H: the
     split wide pipeline with a 128x128 M-writing GEMM). They only pay
     off when the padding (<= tile-1 pairs per class) is small against
     the real pair count - small candidate sets use 16-pair tiles.
