@@ -16,7 +16,8 @@ import sysconfig
 
 REPO = os.path.dirname(os.path.abspath(__file__))
 SRC = [os.path.join(REPO, "coda_amd", "ops", "hip", "pbest.hip"),
-       os.path.join(REPO, "coda_amd", "ops", "hip", "pair.hip")]
+       os.path.join(REPO, "coda_amd", "ops", "hip", "pair.hip"),
+       os.path.join(REPO, "coda_amd", "ops", "hip", "ingest.hip")]
 OUT = os.path.join(REPO, "coda_amd", "ops",
                    "_coda_hip.cpython-310-x86_64-linux-gnu.so")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")

@@ -13,9 +13,22 @@ Additions over the reference:
     loaded to pinned CPU memory and copied to the device on a side stream
     (non_blocking), instead of the reference's single blocking load.
   - synthetic task generator with a planted best model (for tests/benchmarks).
+  - a sharded low-precision format for pools beyond host memory,
+    `<task>.shards/`:
+      manifest.json  {"format": "coda_amd.shards/1", "H", "N", "C",
+                      "dtype": "fp32|fp16|bf16|fp8",
+                      "shards": [{"file", "h0", "h1"}, ...],
+                      "labels": "labels.pt" | null}
+      one torch.save'd contiguous (h1-h0, N, C) tensor per shard in the
+      manifest dtype (fp8 = float8_e4m3fn, the OCP encoding gfx950 uses);
+      shards partition [0, H) in ascending order along the model axis.
+    `Dataset(<dir or manifest>)` streams it chunk by chunk in the file's
+    own dtype through the fused ingest op (ops.ingest_chunk) - see
+    Dataset._init_sharded; `write_sharded_task` writes it.
 """
 from __future__ import annotations
 
+import json
 import os
 from typing import Optional, Tuple
 
@@ -28,6 +41,11 @@ STORAGE_DTYPES = {
     "fp8": torch.float8_e4m3fn,
 }
 
+# on-disk / host-wire dtypes of the sharded format
+WIRE_DTYPES = dict(STORAGE_DTYPES, fp16=torch.float16)
+SHARD_FORMAT = "coda_amd.shards/1"
+MANIFEST_NAME = "manifest.json"
+
 
 class Dataset:
     def __init__(self, filepath: str, device,
@@ -38,7 +56,10 @@ class Dataset:
         """Load a prediction tensor.
 
         Args:
-            filepath: path to the (H, N, C) .pt file.
+            filepath: path to the (H, N, C) .pt file, or to a sharded task
+                (the `<task>.shards/` directory or its manifest.json);
+                for the latter stream_chunk_mb bounds every host chunk
+                (256 when 0; fractions allowed) and `init_stats` is set.
             device: target device.
             shard: optional (rank, world_size); keeps models h with
                 h % world_size == rank.
@@ -54,6 +75,10 @@ class Dataset:
                 (dtype conversion on device), instead of one blocking copy.
         """
         self.device = torch.device(device)
+        if _is_sharded_path(filepath):
+            self._init_sharded(filepath, shard, storage_dtype,
+                               stream_chunk_mb)
+            return
         preds = torch.load(filepath, map_location="cpu", weights_only=True)
         preds = preds.float()
         self.total_models = preds.shape[0]
@@ -78,6 +103,105 @@ class Dataset:
             labels = torch.load(label_p, map_location="cpu", weights_only=True)
             self.labels = labels.to(self.device)
 
+    def _init_sharded(self, path, shard, storage_dtype, stream_chunk_mb):
+        """Load a `<task>.shards/` directory (format: module docstring).
+
+        The host never holds more than two chunks, in the file's own
+        dtype: each shard is opened with mmap, bounded chunks (at most
+        `stream_chunk_mb` MB, 256 when 0; sub-split along the point axis
+        when one model exceeds that) are staged through two pinned
+        buffers, copied on a side stream, and handed to ops.ingest_chunk
+        on that stream - one fused pass that rounds to the storage dtype
+        and produces the selector's init statistics (`init_stats`) and,
+        HBM headroom permitting, the class-major mirror. On a CPU device
+        the same loop runs with the eager twin."""
+        from . import ops
+        from .util import mirror_fits
+
+        man = read_shard_manifest(path)
+        root = man["root"]
+        H, N, C = man["H"], man["N"], man["C"]
+        wire_dt = WIRE_DTYPES[man["dtype"]]
+        dt = STORAGE_DTYPES[storage_dtype]
+        dev = self.device
+        self.total_models = H
+        self.shard = shard
+        rank, world = shard if shard is not None else (0, 1)
+        self.model_idxs = torch.arange(rank, H, world)
+        self.storage_dtype = storage_dtype
+        Hl = self.model_idxs.numel()
+
+        esize = torch.empty(0, dtype=wire_dt).element_size()
+        budget = max(1, int((stream_chunk_mb or 256) * (1 << 20)))
+        per_model = N * C * esize
+        if per_model <= budget:
+            rows, npts = max(1, budget // per_model), N
+        else:
+            rows, npts = 1, max(1, budget // (C * esize))
+
+        on_gpu = dev.type == "cuda"
+        pool_bytes = Hl * N * C * torch.empty(0, dtype=dt).element_size()
+        want_t = (on_gpu and ops.hip_available()
+                  and mirror_fits(dev, pool_bytes, pool_resident=False))
+        preds = torch.empty((Hl, N, C), dtype=dt, device=dev)
+        classes = torch.empty((Hl, N), dtype=torch.long, device=dev)
+        ens = torch.zeros((N, C), dtype=torch.float32, device=dev)
+        preds_t = (torch.empty((Hl, C, N), dtype=dt, device=dev)
+                   if want_t else None)
+
+        if on_gpu:
+            side = torch.cuda.Stream(device=dev)
+            side.wait_stream(torch.cuda.current_stream(dev))  # ens zeros
+            bufs = [torch.empty(min(rows, max(Hl, 1)) * npts * C,
+                                dtype=wire_dt).pin_memory()
+                    for _ in range(2)]
+            events = [torch.cuda.Event(), torch.cuda.Event()]
+            for e in events:
+                e.record(side)
+        i = 0
+        for sh in man["shards"]:
+            # local models inside this shard: h = rank + l * world
+            l0 = -(-(sh["h0"] - rank) // world) if sh["h0"] > rank else 0
+            l1 = min(Hl, -(-(sh["h1"] - rank) // world))
+            if l1 <= l0:
+                continue
+            t = torch.load(os.path.join(root, sh["file"]),
+                           map_location="cpu", weights_only=True, mmap=True)
+            _check_shard_tensor(t, sh, N, C, wire_dt)
+            for la in range(l0, l1, rows):
+                lb = min(la + rows, l1)
+                a = rank + la * world - sh["h0"]
+                b = rank + (lb - 1) * world - sh["h0"] + 1
+                for n0 in range(0, N, npts):
+                    n1 = min(n0 + npts, N)
+                    src = t[a:b:world, n0:n1]
+                    if not on_gpu:
+                        ops.ingest_chunk(src.contiguous(), la, n0, preds,
+                                         classes, ens, preds_t)
+                        continue
+                    k = i % 2
+                    i += 1
+                    events[k].synchronize()  # buffer free to reuse
+                    stage = bufs[k][:src.numel()].view(src.shape)
+                    stage.copy_(src)
+                    with torch.cuda.stream(side):
+                        wire = stage.to(dev, non_blocking=True)
+                        ops.ingest_chunk(wire, la, n0, preds, classes, ens,
+                                         preds_t)
+                        events[k].record(side)
+            del t
+        if on_gpu:
+            torch.cuda.current_stream(dev).wait_stream(side)
+
+        self.preds = preds
+        self.init_stats = {"classes": classes, "ens_sum": ens,
+                           "preds_t": preds_t}
+        self.labels = None
+        if man["labels"] is not None:
+            labels = torch.load(os.path.join(root, man["labels"]),
+                                map_location="cpu", weights_only=True)
+            self.labels = labels.to(dev)
+
     @classmethod
     def from_tensors(cls, preds: torch.Tensor, labels: Optional[torch.Tensor],
                      device, shard: Optional[Tuple[int, int]] = None):
@@ -101,6 +225,127 @@ class Dataset:
         self.preds = preds.to(self.device)
         self.labels = labels.to(self.device) if labels is not None else None
         return self
+
+
+def resolve_task_path(data_dir: str, task: str) -> str:
+    """`<data_dir>/<task>.pt` when it exists (as always); only when it is
+    missing, `<data_dir>/<task>.shards` if that holds a manifest."""
+    pt = os.path.join(data_dir, task + ".pt")
+    if not os.path.exists(pt):
+        shards = os.path.join(data_dir, task + ".shards")
+        if os.path.exists(os.path.join(shards, MANIFEST_NAME)):
+            return shards
+    return pt
+
+
+def _is_sharded_path(path: str) -> bool:
+    return os.path.isdir(path) or os.path.basename(path) == MANIFEST_NAME
+
+
+def read_shard_manifest(path: str) -> dict:
+    """Read and validate `<task>.shards/manifest.json` (path may be the
+    directory or the manifest). Returns the manifest with a `root` key
+    (the directory); raises ValueError on an unknown format or dtype, or
+    shards that do not partition [0, H) in ascending order."""
+    root = path if os.path.isdir(path) else os.path.dirname(path)
+    mpath = os.path.join(root, MANIFEST_NAME)
+    if not os.path.exists(mpath):
+        raise FileNotFoundError(f"no {MANIFEST_NAME} in {root}")
+    with open(mpath) as f:
+        man = json.load(f)
+    if man.get("format") != SHARD_FORMAT:
+        raise ValueError(f"{mpath}: unknown format {man.get('format')!r} "
+                         f"(expected {SHARD_FORMAT!r})")
+    if man.get("dtype") not in WIRE_DTYPES:
+        raise ValueError(f"{mpath}: unknown dtype {man.get('dtype')!r} "
+                         f"(expected one of {sorted(WIRE_DTYPES)})")
+    for k in ("H", "N", "C"):
+        if not isinstance(man.get(k), int) or man[k] <= 0:
+            raise ValueError(f"{mpath}: {k} must be a positive integer")
+    shards = man.get("shards")
+    if not isinstance(shards, list) or not shards:
+        raise ValueError(f"{mpath}: no shards listed")
+    at = 0
+    for sh in shards:
+        h0, h1 = sh.get("h0"), sh.get("h1")
+        if not (isinstance(h0, int) and isinstance(h1, int) and h0 < h1
+                and isinstance(sh.get("file"), str)):
+            raise ValueError(f"{mpath}: malformed shard entry {sh!r}")
+        if h0 > at:
+            raise ValueError(f"{mpath}: gap in model ranges - models "
+                             f"[{at}, {h0}) are in no shard")
+        if h0 < at:
+            raise ValueError(f"{mpath}: shard {sh['file']} [{h0}, {h1}) "
+                             f"overlaps the models before {at}")
+        at = h1
+    if at != man["H"]:
+        raise ValueError(f"{mpath}: shards cover [0, {at}) but H = "
+                         f"{man['H']}")
+    man.setdefault("labels", None)
+    man["root"] = root
+    return man
+
+
+def _check_shard_tensor(t, sh, N, C, wire_dt):
+    want = (sh["h1"] - sh["h0"], N, C)
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) != want:
+        got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)
+        raise ValueError(f"shard {sh['file']}: shape {got} does not match "
+                         f"the manifest's {want}")
+    if t.dtype != wire_dt:
+        raise ValueError(f"shard {sh['file']}: dtype {t.dtype} does not "
+                         f"match the manifest's {wire_dt}")
+
+
+def write_sharded_task(out_dir: str, shard_iter_or_tensor, dtype: str,
+                       models_per_shard: int = 16, labels=None) -> str:
+    """Write a `<task>.shards/` directory in on-disk dtype `dtype`
+    ("fp32" | "fp16" | "bf16" | "fp8").
+
+    The source is either one (H, N, C) tensor (an mmap'd one is fine: it
+    is cut into `models_per_shard`-model slices, converted one at a time)
+    or an iterable of (k, N, C) tensors, each written as one shard. No
+    full-size copy is made. Returns the manifest path."""
+    if dtype not in WIRE_DTYPES:
+        raise ValueError(f"unknown dtype {dtype!r} "
+                         f"(expected one of {sorted(WIRE_DTYPES)})")
+    dt = WIRE_DTYPES[dtype]
+    if isinstance(shard_iter_or_tensor, torch.Tensor):
+        src = shard_iter_or_tensor
+        if src.dim() != 3:
+            raise ValueError("expected an (H, N, C) tensor")
+        k = max(1, int(models_per_shard))
+        pieces = (src[h:h + k] for h in range(0, src.shape[0], k))
+    else:
+        pieces = iter(shard_iter_or_tensor)
+    os.makedirs(out_dir, exist_ok=True)
+    shards, at, N, C = [], 0, None, None
+    for piece in pieces:
+        if piece.dim() != 3 or piece.shape[0] == 0:
+            raise ValueError("each shard must be a non-empty (k, N, C) tensor")
+        if N is None:
+            N, C = int(piece.shape[1]), int(piece.shape[2])
+        elif (int(piece.shape[1]), int(piece.shape[2])) != (N, C):
+            raise ValueError("shards disagree on (N, C)")
+        out = piece if piece.dtype == dt else piece.float().to(dt)
+        h1 = at + int(piece.shape[0])
+        name = f"h{at:06d}-{h1:06d}.pt"
+        # clone: a slice would drag its whole backing storage into the file
+        torch.save(out.contiguous().clone(), os.path.join(out_dir, name))
+        shards.append({"file": name, "h0": at, "h1": h1})
+        at = h1
+    if not shards:
+        raise ValueError("no shards to write")
+    label_name = None
+    if labels is not None:
+        label_name = "labels.pt"
+        torch.save(labels.cpu().clone(), os.path.join(out_dir, label_name))
+    man = {"format": SHARD_FORMAT, "H": at, "N": N, "C": C, "dtype": dtype,
+           "shards": shards, "labels": label_name}
+    mpath = os.path.join(out_dir, MANIFEST_NAME)
+    with open(mpath, "w") as f:
+        json.dump(man, f, indent=1)
+    return mpath
 
 
 def _stream_to_device(t: torch.Tensor, device: torch.device,

@@ -65,6 +65,23 @@ def _want_hip(t: torch.Tensor) -> bool:
         f"the gfx950 kernels. Import error: {_ext_err}")
 
 
+def ingest_chunk(wire: torch.Tensor, h0: int, n0: int,
+                 preds_out: torch.Tensor, classes_out: torch.Tensor,
+                 ens_out: torch.Tensor,
+                 preds_t_out: torch.Tensor = None) -> None:
+    """Fused pool ingest of one wire-dtype chunk (contract:
+    reference.ingest_chunk). On a ROCm device this is one gfx950 kernel
+    pass (ingest.hip) that rounds to the storage dtype, takes the argmax
+    classes, advances the consensus sum and optionally writes the
+    class-major mirror; all outputs are bit-equal to the eager twin."""
+    if _want_hip(preds_out):
+        _ext.ingest_chunk(wire, int(h0), int(n0), preds_out, classes_out,
+                          ens_out, preds_t_out)
+        return
+    reference.ingest_chunk(wire, h0, n0, preds_out, classes_out, ens_out,
+                           preds_t_out)
+
+
 def pbest_from_beta(alpha: torch.Tensor, beta: torch.Tensor,
                     num_points: int = PBEST_NUM_POINTS,
                     return_unnormalized: bool = False) -> torch.Tensor:

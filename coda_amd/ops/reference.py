@@ -65,6 +65,30 @@ def init_model_stats(preds: torch.Tensor, chunk_h: int = 0):
     return classes, ens
 
 
+def ingest_chunk(wire: torch.Tensor, h0: int, n0: int,
+                 preds_out: torch.Tensor, classes_out: torch.Tensor,
+                 ens_out: torch.Tensor,
+                 preds_t_out: torch.Tensor = None) -> None:
+    """Fused pool ingest of one (hc, nc, C) wire-dtype chunk covering local
+    models h0..h0+hc and points n0..n0+nc (eager twin of ingest.hip).
+
+    With s = wire rounded to the storage dtype of preds_out and f = s in
+    fp32: stores s into preds_out (and, class-major, into preds_t_out),
+    the lowest-index argmax of f into classes_out, and advances ens_out by
+    the plain left-to-right fp32 sum over h ascending - one add per model,
+    so the result does not depend on how the pool is chunked."""
+    hc, nc, _ = wire.shape
+    s = wire.float().to(preds_out.dtype)
+    f = s.float()
+    preds_out[h0:h0 + hc, n0:n0 + nc] = s
+    if preds_t_out is not None:
+        preds_t_out[h0:h0 + hc, :, n0:n0 + nc] = s.permute(0, 2, 1)
+    classes_out[h0:h0 + hc, n0:n0 + nc] = f.argmax(-1)
+    acc = ens_out[n0:n0 + nc]
+    for h in range(hc):
+        acc += f[h]
+
+
 def confusion_prior(pseudo_labels: torch.Tensor, preds: torch.Tensor) -> torch.Tensor:
     """Soft confusion matrices from pseudo-labels: (N,), (H,N,C) -> (H,C,C).
 

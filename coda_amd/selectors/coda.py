@@ -31,7 +31,7 @@ from ..base import ModelSelector
 from ..parallel import Comm, get_comm
 from .. import ops
 from ..ops import sharded as shops
-from ..util import DEBUG, _check
+from ..util import DEBUG, _check, mirror_fits
 
 import os
 DEBUG_VIZ = os.environ.get("CODA_AMD_DEBUG_VIZ") == "1"
@@ -97,7 +97,18 @@ class CODA(ModelSelector):
         preds = dataset.preds
         # one chunked fp32-upcast pass: cached argmax classes (Hl, N) +
         # consensus sum (storage may be fp32/bf16/fp8)
-        self.classes, ens_sum = ops.init_model_stats(preds)
+        # - unless the loader's fused ingest already produced them (sharded
+        # tasks: datasets.Dataset.init_stats), in which case neither the
+        # stats nor the mirror below are recomputed
+        stats = getattr(dataset, "init_stats", None)
+        if (stats is not None
+                and tuple(stats["classes"].shape) == (self.Hl, self.N)
+                and tuple(stats["ens_sum"].shape) == (self.N, self.C)):
+            self.classes = stats["classes"]
+            ens_sum = stats["ens_sum"].clone()  # all-reduced in place below
+        else:
+            stats = None
+            self.classes, ens_sum = ops.init_model_stats(preds)
 
         # Sharded pair engine = "replicated Betas, sharded candidates":
         # every rank keeps the global (H, C) diagonal-Beta view + the
@@ -140,11 +151,13 @@ class CODA(ModelSelector):
         # has the pool's size + 24 GB headroom to spare (the 128 GB
         # fp8 million-point pool deliberately skips it).
         self._preds_t = None
-        if preds.is_cuda and ops.hip_available() and preds.dim() == 3:
+        if stats is not None:
+            # built (or skipped, under the same headroom rule) at ingest
+            self._preds_t = stats.get("preds_t")
+        elif preds.is_cuda and ops.hip_available() and preds.dim() == 3:
             try:
-                free, _ = torch.cuda.mem_get_info(self.device)
                 need = preds.numel() * preds.element_size()
-                if free > need + 24 * (1 << 30):
+                if mirror_fits(self.device, need):
                     self._preds_t = preds.permute(0, 2, 1).contiguous()
             except (RuntimeError, torch.OutOfMemoryError):
                 self._preds_t = None

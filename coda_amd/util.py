@@ -34,6 +34,21 @@ def set_debug(enabled: bool) -> None:
     _coda.DEBUG = enabled
 
 
+MIRROR_SPARE_BYTES = 24 * (1 << 30)
+
+
+def mirror_fits(device, pool_bytes: int, pool_resident: bool = True) -> bool:
+    """HBM-headroom rule for the class-major (H, C, N) pool mirror: build
+    it only when, with the pool and the mirror both resident, 24 GB stay
+    free (the 128 GB fp8 million-point pool deliberately skips it).
+
+    pool_resident=False asks before the pool itself is allocated (the
+    sharded loader builds both during ingest)."""
+    free, _ = torch.cuda.mem_get_info(device)
+    need = pool_bytes if pool_resident else 2 * pool_bytes
+    return free > need + MIRROR_SPARE_BYTES
+
+
 class Ensemble:
     """Mean-ensemble consensus over the model axis (reference
     coda/util.py:7-14)."""

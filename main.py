@@ -26,6 +26,7 @@ import torch
 from tqdm import tqdm
 
 from coda_amd import CODA, Dataset, Oracle
+from coda_amd.datasets import resolve_task_path
 from coda_amd.baselines import (IID, ActiveTesting, VMA, ModelPicker,
                                 Uncertainty, TASK_EPS)
 from coda_amd.options import LOSS_FNS
@@ -99,7 +100,8 @@ def parse_args(argv=None):
                              "always upcasts to fp32).")
     parser.add_argument("--stream-chunk-mb", type=int, default=0,
                         help="Stream the pool host->HBM through pinned "
-                             "buffers of this size (0 = one blocking copy).")
+                             "buffers of this size (0 = one blocking copy; "
+                             "sharded tasks always stream, 256 when 0).")
     parser.add_argument("--checkpoint-every", type=int, default=0,
                         help="Save selector state every K steps (0 = off); "
                              "an interrupted seed resumes mid-run.")
@@ -246,7 +248,8 @@ def main(argv=None):
         print("device is", device)
 
     shard = (comm.rank, comm.world) if comm.is_distributed else None
-    dataset = Dataset(os.path.join(args.data_dir, args.task + ".pt"),
+    # <data-dir>/<task>.pt first; <task>.shards/ only when that is missing
+    dataset = Dataset(resolve_task_path(args.data_dir, args.task),
                       device=device, shard=shard,
                       storage_dtype=args.storage,
                       stream_chunk_mb=args.stream_chunk_mb)

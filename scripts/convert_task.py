@@ -9,6 +9,13 @@ Usage:
     python scripts/convert_task.py --task T [--data-dir data]
         [--dtype bf16|fp8] [--out-dir data_bf16]
     python scripts/convert_task.py --all --data-dir data --dtype fp8
+    python scripts/convert_task.py --task T --dtype fp8 --shards
+        [--models-per-shard 16]
+
+--shards writes the sharded format `<out-dir>/<task>.shards/`
+(coda_amd/datasets.py) instead of one .pt: the source is opened with mmap
+and converted one shard at a time, so no full-size copy - fp32 or
+otherwise - is ever made. That is the route for pools beyond host memory.
 """
 from __future__ import annotations
 
@@ -21,7 +28,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from coda_amd.datasets import STORAGE_DTYPES  # noqa: E402
+from coda_amd.datasets import (STORAGE_DTYPES, WIRE_DTYPES,  # noqa: E402
+                               write_sharded_task)
 
 
 def convert(task: str, data_dir: str, out_dir: str, dtype: str):
@@ -38,14 +46,34 @@ def convert(task: str, data_dir: str, out_dir: str, dtype: str):
           f"{os.path.getsize(dst)/1e6:.1f} MB ({dtype})")
 
 
+def convert_shards(task: str, data_dir: str, out_dir: str, dtype: str,
+                   models_per_shard: int):
+    src = os.path.join(data_dir, task + ".pt")
+    dst = os.path.join(out_dir, task + ".shards")
+    t = torch.load(src, map_location="cpu", weights_only=True, mmap=True)
+    labels = None
+    lbl = src.replace(".pt", "_labels.pt")
+    if os.path.exists(lbl):
+        labels = torch.load(lbl, map_location="cpu", weights_only=True)
+    write_sharded_task(dst, t, dtype, models_per_shard, labels=labels)
+    n = -(-t.shape[0] // models_per_shard)
+    print(f"{task}: {os.path.getsize(src)/1e6:.1f} MB -> {n} shard(s) of "
+          f"<= {models_per_shard} models ({dtype}) in {dst}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--task", default=None)
     ap.add_argument("--all", action="store_true")
     ap.add_argument("--data-dir", default="data")
-    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8"])
+    ap.add_argument("--dtype", default="bf16", choices=sorted(WIRE_DTYPES))
     ap.add_argument("--out-dir", default=None)
+    ap.add_argument("--shards", action="store_true",
+                    help="write <task>.shards/ instead of one .pt")
+    ap.add_argument("--models-per-shard", type=int, default=16)
     args = ap.parse_args()
+    if not args.shards and args.dtype not in STORAGE_DTYPES:
+        ap.error(f"--dtype {args.dtype} needs --shards")
     out_dir = args.out_dir or f"{args.data_dir}_{args.dtype}"
     if args.all:
         tasks = sorted(f[:-3] for f in os.listdir(args.data_dir)
@@ -55,7 +83,11 @@ def main():
         assert args.task, "--task or --all"
         tasks = [args.task]
     for t in tasks:
-        convert(t, args.data_dir, out_dir, args.dtype)
+        if args.shards:
+            convert_shards(t, args.data_dir, out_dir, args.dtype,
+                           args.models_per_shard)
+        else:
+            convert(t, args.data_dir, out_dir, args.dtype)
 
 
 if __name__ == "__main__":
