@@ -17,7 +17,10 @@ import sysconfig
 REPO = os.path.dirname(os.path.abspath(__file__))
 SRC = [os.path.join(REPO, "coda_amd", "ops", "hip", "pbest.hip"),
        os.path.join(REPO, "coda_amd", "ops", "hip", "pair.hip"),
-       os.path.join(REPO, "coda_amd", "ops", "hip", "ingest.hip")]
+       os.path.join(REPO, "coda_amd", "ops", "hip", "ingest.hip"),
+       os.path.join(REPO, "coda_amd", "ops", "hip", "ingest_f16.hip")]
+# headers the sources include: part of the up-to-date check only
+HDR = [os.path.join(REPO, "coda_amd", "ops", "hip", "ingest_kernel.h")]
 OUT = os.path.join(REPO, "coda_amd", "ops",
                    "_coda_hip.cpython-310-x86_64-linux-gnu.so")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
@@ -28,7 +31,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     import torch.utils.cpp_extension as ce
 
     if not force and os.path.exists(OUT):
-        newest_src = max(os.path.getmtime(s) for s in SRC + [__file__])
+        newest_src = max(os.path.getmtime(s) for s in SRC + HDR + [__file__])
         if os.path.getmtime(OUT) >= newest_src:
             if verbose:
                 print(f"[build_hip] build_mode=reuse (up to date): {OUT}")

@@ -29,7 +29,7 @@ class ActiveTesting(IID):
 
         # surrogate = ensemble mean; static per-point acquisition mass:
         # sum_h (1 - pi_y[n, argmax_h(n)])
-        pi_y = dataset.preds.mean(dim=0)                      # (N, C)
+        pi_y = ops.ensemble_mean(dataset.preds)               # (N, C)
         y_star = pi_y.gather(1, self.classes.t())             # (N, Hl)
         self._acq_mass = (1.0 - y_star).sum(dim=1)            # (N,)
 

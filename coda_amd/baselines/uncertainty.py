@@ -15,7 +15,7 @@ from .. import ops
 
 def uncertainty(preds: torch.Tensor, d_u_idxs) -> torch.Tensor:
     """Reference-parity helper: entropy of the ensemble mean on a subset."""
-    ent = ops.entropy_acquisition(preds.mean(dim=0))
+    ent = ops.entropy_acquisition(ops.ensemble_mean(preds))
     return ent[d_u_idxs]
 
 
@@ -23,7 +23,8 @@ class Uncertainty(IID):
     def __init__(self, dataset, loss_fn):
         super().__init__(dataset, loss_fn)
         self.stochastic = False
-        self._entropy = ops.entropy_acquisition(dataset.preds.mean(dim=0))
+        self._entropy = ops.entropy_acquisition(
+            ops.ensemble_mean(dataset.preds))
 
     def get_next_item_to_label(self):
         ent = self._entropy[self.d_u_idxs]

@@ -23,7 +23,7 @@ class VMA(ActiveTesting):
         super().__init__(dataset, loss_fn)
         # Static per-point pairwise-difference mass (the surrogate and the
         # argmax classes never change).
-        pi_y = dataset.preds.mean(dim=0)                  # (N, C)
+        pi_y = ops.ensemble_mean(dataset.preds)           # (N, C)
         y_star = pi_y.gather(1, self.classes.t()).t()     # (Hl, N)
         self._vma_mass = ops.vma_pairwise(1.0 - y_star)   # (N,)
 

@@ -4,7 +4,8 @@ On-disk format (identical to the reference, coda/datasets.py:4-23): a
 `<task>.pt` tensor of shape (H, N, C) holding post-softmax scores - H models,
 N points, C classes - optionally with `<task>_labels.pt` holding (N,) integer
 ground-truth labels. Stored dtype may be fp16/bf16; compute is always fp32
-(the loader up-casts).
+(the loader up-casts, or - storage_dtype="fp16" - keeps the fp16 bits and
+every consumer up-casts, which is the same computation at half the bytes).
 
 Additions over the reference:
   - model-axis sharding for multi-GPU runs (`shard` argument): rank r keeps
@@ -37,12 +38,16 @@ import torch
 
 STORAGE_DTYPES = {
     "fp32": torch.float32,
+    "fp16": torch.float16,
     "bf16": torch.bfloat16,
     "fp8": torch.float8_e4m3fn,
 }
 
 # on-disk / host-wire dtypes of the sharded format
-WIRE_DTYPES = dict(STORAGE_DTYPES, fp16=torch.float16)
+WIRE_DTYPES = dict(STORAGE_DTYPES)
+# in-memory pools Dataset.from_tensors keeps when no storage dtype is asked
+# for; an fp16 tensor is up-cast there, like an fp16 file by default
+_KEPT_DTYPES = (torch.float32, torch.bfloat16, torch.float8_e4m3fn)
 SHARD_FORMAT = "coda_amd.shards/1"
 MANIFEST_NAME = "manifest.json"
 
@@ -65,11 +70,15 @@ class Dataset:
                 h % world_size == rank.
             pin: stage through pinned host memory with an async copy.
             storage_dtype: on-device storage format - "fp32" (reference
-                parity), "bf16" or "fp8" (e4m3). Compute always up-casts
-                to fp32 (the reference's own fp16-on-disk -> .float()
-                pattern, coda/datasets.py:14, generalized). Halving /
-                quartering storage is what fits large model pools into
-                the 288 GB of HBM3E.
+                parity), "fp16", "bf16" or "fp8" (e4m3). Compute always
+                up-casts to fp32 (the reference's own fp16-on-disk ->
+                .float() pattern, coda/datasets.py:14, generalized).
+                Halving / quartering storage is what fits large model
+                pools into the 288 GB of HBM3E. "fp16" is lossless for
+                fp16 source data (the benchmark files) at half of fp32:
+                fp16 -> fp32 is exact, so a run on it computes what the
+                fp32-stored run computes. An fp16 .pt file then skips
+                the host up-cast and is staged and copied as fp16.
             stream_chunk_mb: >0 streams the tensor host->device in chunks
                 of this size through pinned buffers on a side stream
                 (dtype conversion on device), instead of one blocking copy.
@@ -80,7 +89,11 @@ class Dataset:
                                stream_chunk_mb)
             return
         preds = torch.load(filepath, map_location="cpu", weights_only=True)
-        preds = preds.float()
+        dt = STORAGE_DTYPES[storage_dtype]
+        # an fp16 file bound for fp16 storage stays fp16 on the host, on
+        # the wire and on the device; anything else goes through fp32
+        if not (dt == torch.float16 and preds.dtype == dt):
+            preds = preds.float()
         self.total_models = preds.shape[0]
         self.shard = shard
         if shard is not None:
@@ -90,7 +103,6 @@ class Dataset:
         else:
             self.model_idxs = torch.arange(self.total_models)
         self.storage_dtype = storage_dtype
-        dt = STORAGE_DTYPES[storage_dtype]
         if stream_chunk_mb and self.device.type == "cuda":
             self.preds = _stream_to_device(preds, self.device, dt,
                                            stream_chunk_mb)
@@ -204,15 +216,24 @@ class Dataset:
 
     @classmethod
     def from_tensors(cls, preds: torch.Tensor, labels: Optional[torch.Tensor],
-                     device, shard: Optional[Tuple[int, int]] = None):
+                     device, shard: Optional[Tuple[int, int]] = None,
+                     storage_dtype: Optional[str] = None):
         """Build a Dataset from in-memory tensors (tests, synthetic tasks).
 
-        A tensor already in a storage dtype (bf16 / fp8-e4m3) is kept as
-        is - up-casting a 1M-point fp8 pool to fp32 would be 512 GB.
+        A tensor already in fp32 / bf16 / fp8-e4m3 is kept as is -
+        up-casting a 1M-point fp8 pool to fp32 would be 512 GB; any other
+        dtype, fp16 included, is up-cast to fp32. storage_dtype, when
+        given, names the storage dtype instead: the pool is converted to
+        it (through fp32), or kept if it already has that dtype.
         """
         self = cls.__new__(cls)
         self.device = torch.device(device)
-        if preds.dtype not in STORAGE_DTYPES.values():
+        if storage_dtype is not None:
+            dt = STORAGE_DTYPES[storage_dtype]
+            if preds.dtype != dt:
+                preds = preds.float().to(dt)
+            self.storage_dtype = storage_dtype
+        elif preds.dtype not in _KEPT_DTYPES:
             preds = preds.float()
         self.total_models = preds.shape[0]
         self.shard = shard
@@ -351,8 +372,9 @@ def write_sharded_task(out_dir: str, shard_iter_or_tensor, dtype: str,
 def _stream_to_device(t: torch.Tensor, device: torch.device,
                       dtype: torch.dtype, chunk_mb: int) -> torch.Tensor:
     """Pinned double-buffered host->HBM streaming with on-device dtype
-    conversion (fp32 on the host wire here; a bf16/fp8 source file would
-    halve wire bytes too). Chunks along the model axis."""
+    conversion (the host wire is t's dtype: fp32, or fp16 for an fp16
+    file bound for fp16 storage, which needs no conversion). Chunks along
+    the model axis."""
     H = t.shape[0]
     out = torch.empty(t.shape, dtype=dtype, device=device)
     bytes_per_model = t[0].numel() * t.element_size()

@@ -24,7 +24,7 @@ from .reference import (  # re-export cheap ops + constants
     consensus, confusion_prior, init_dirichlets, dirichlet_to_beta,
     pi_hat_partial, pi_hat_pack, pi_hat_pack_chunked,
     pi_hat_partial_packed, pi_hat_partial_streamed, pi_hat_normalize,
-    pbest_from_beta_hchunked, init_model_stats,
+    pbest_from_beta_hchunked, init_model_stats, ensemble_mean,
     beta_grid_pdf_cdf, hypothetical_betas,
     mixture_entropy as _mixture_entropy_eager,
     pred_classes, disagreement_mask,
@@ -164,8 +164,8 @@ def pi_hat_delta(preds: torch.Tensor, point_classes: torch.Tensor,
     mirror makes the same read a coalesced stream (~15x). The kernels
     share the accumulation pattern, so the route is bitwise-neutral."""
     if (preds.is_cuda and preds.is_contiguous()
-            and preds.dtype in (torch.float32, torch.bfloat16,
-                                torch.float8_e4m3fn)
+            and preds.dtype in (torch.float32, torch.float16,
+                                torch.bfloat16, torch.float8_e4m3fn)
             and _want_hip(preds)):
         cls32 = point_classes.to(torch.int32).contiguous()
         H, N = preds.shape[0], preds.shape[1]

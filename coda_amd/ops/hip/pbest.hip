@@ -1199,7 +1199,9 @@ trc_rows_kernel(const float* __restrict__ eg,    // (H, 2, P)
 // per-label posterior-marginal change (only Dirichlet row true_class
 // moves; coda/coda.py:316-317). One thread per point; consecutive
 // threads read consecutive n (coalesced); the class index is
-// wave-uniform per model. fp32 and bf16 prediction storage.
+// wave-uniform per model. fp32, fp16, bf16 and fp8 prediction storage;
+// every dtype up-casts exactly, so fp16 storage of an fp16-representable
+// pool sums the very fp32 values the fp32 kernel does.
 template <typename T>
 __global__ void __launch_bounds__(BLOCK)
 pi_hat_delta_kernel(const T* __restrict__ preds,  // (H, N, C)
@@ -1310,70 +1312,25 @@ pi_hat_delta_t_part_kernel(const T* __restrict__ preds_t, // (H, C, N)
 
 // pi marginal: out[c] = sum_n adjusted[n, c] / max(row_sums[n], 1e-12)
 // (reference coda/coda.py:229-233 without materializing the normalized
-// (N, C) matrix). One streaming pass: each thread owns fixed columns
-// c = tid + k*BLOCK (register accumulators, no LDS), blocks stride over
-// row slabs, one atomicAdd per (block, column) at the end.
+// (N, C) matrix). Slab partials for every shape the vector kernel below
+// does not take (C % 4 != 0, or 1024 < C <= 2048): each thread owns fixed
+// columns c = tid + k*BLOCK (register accumulators, no LDS), a block
+// streams its row slab and stores one partial row (G, Cpad), pad columns
+// zeroed; pi_marginal_reduce_kernel sums the slabs in a fixed order. The
+// earlier schedule ended in one atomicAdd per (block, column), whose
+// order - and with it the low bits of pi_hat and of everything computed
+// from it - changed from run to run.
 __global__ void __launch_bounds__(BLOCK)
 pi_marginal_kernel(const float* __restrict__ adjusted,  // (N, C)
                    const float* __restrict__ row_sums,  // (N,)
-                   float* __restrict__ out,             // (C,) pre-zeroed
-                   long long N, int C) {
+                   float* __restrict__ partial,         // (G, Cpad)
+                   long long N, int C, int Cpad) {
     const int tid = threadIdx.x;
     const long long rows_per_block =
         (N + gridDim.x - 1) / gridDim.x;
     const long long n0 = (long long)blockIdx.x * rows_per_block;
     const long long n1 = min(n0 + rows_per_block, N);
-    if ((C & 3) == 0 && C <= 4 * BLOCK) {
-        // vector path: thread tid owns columns [4*tid, 4*tid+4) as ONE
-        // float4 per row - 4x wider transactions than the scalar path
-        // (the (N, C) read is this kernel's whole cost at large N)
-        const int c4 = tid * 4;
-        if (c4 < C) {
-            // two accumulator sets x 4-row unroll: 4 row-loads in
-            // flight per lane and no serial add chain (measured 173 us
-            // at 2-row/1-acc vs a ~25 us traffic floor)
-            float4 acc = {0.f, 0.f, 0.f, 0.f};
-            float4 acc2 = {0.f, 0.f, 0.f, 0.f};
-            long long n = n0;
-            for (; n + 3 < n1; n += 4) {
-                const float i0 = 1.0f / fmaxf(row_sums[n], 1e-12f);
-                const float i1 = 1.0f / fmaxf(row_sums[n + 1], 1e-12f);
-                const float i2 = 1.0f / fmaxf(row_sums[n + 2], 1e-12f);
-                const float i3 = 1.0f / fmaxf(row_sums[n + 3], 1e-12f);
-                const float4 v0 = *reinterpret_cast<const float4*>(
-                    adjusted + n * C + c4);
-                const float4 v1 = *reinterpret_cast<const float4*>(
-                    adjusted + (n + 1) * C + c4);
-                const float4 v2 = *reinterpret_cast<const float4*>(
-                    adjusted + (n + 2) * C + c4);
-                const float4 v3 = *reinterpret_cast<const float4*>(
-                    adjusted + (n + 3) * C + c4);
-                acc.x += v0.x * i0 + v1.x * i1;
-                acc.y += v0.y * i0 + v1.y * i1;
-                acc.z += v0.z * i0 + v1.z * i1;
-                acc.w += v0.w * i0 + v1.w * i1;
-                acc2.x += v2.x * i2 + v3.x * i3;
-                acc2.y += v2.y * i2 + v3.y * i3;
-                acc2.z += v2.z * i2 + v3.z * i3;
-                acc2.w += v2.w * i2 + v3.w * i3;
-            }
-            for (; n < n1; ++n) {
-                const float inv = 1.0f / fmaxf(row_sums[n], 1e-12f);
-                const float4 v = *reinterpret_cast<const float4*>(
-                    adjusted + n * C + c4);
-                acc.x += v.x * inv; acc.y += v.y * inv;
-                acc.z += v.z * inv; acc.w += v.w * inv;
-            }
-            acc.x += acc2.x; acc.y += acc2.y;
-            acc.z += acc2.z; acc.w += acc2.w;
-            atomicAdd(out + c4 + 0, acc.x);
-            atomicAdd(out + c4 + 1, acc.y);
-            atomicAdd(out + c4 + 2, acc.z);
-            atomicAdd(out + c4 + 3, acc.w);
-        }
-        return;
-    }
-    const int ncols = (C + BLOCK - 1) / BLOCK;
+    const int ncols = (Cpad + BLOCK - 1) / BLOCK;
     float acc[8];  // supports C <= 8*BLOCK = 2048
     for (int k = 0; k < ncols && k < 8; ++k) acc[k] = 0.f;
     long long n = n0;
@@ -1395,9 +1352,11 @@ pi_marginal_kernel(const float* __restrict__ adjusted,  // (N, C)
             if (c < C) acc[k] += row[c] * inv;
         }
     }
+    // an empty slab (more blocks than rows) stores its zeros too
+    float* prow = partial + (long long)blockIdx.x * Cpad;
     for (int k = 0; k < ncols && k < 8; ++k) {
         const int c = tid + k * BLOCK;
-        if (c < C) atomicAdd(out + c, acc[k]);
+        if (c < Cpad) prow[c] = acc[k];
     }
 }
 
@@ -2130,6 +2089,13 @@ torch::Tensor pi_hat_delta(torch::Tensor preds, torch::Tensor cls) {
                                preds.data_ptr()),
                            cls.data_ptr<int>(), out.data_ptr<float>(),
                            H, N, C);
+    } else if (preds.scalar_type() == torch::kFloat16) {
+        hipLaunchKernelGGL(pi_hat_delta_kernel<_Float16>, dim3(blocks),
+                           dim3(BLOCK), 0, stream.stream(),
+                           reinterpret_cast<const _Float16*>(
+                               preds.data_ptr()),
+                           cls.data_ptr<int>(), out.data_ptr<float>(),
+                           H, N, C);
     } else if (preds.scalar_type() == torch::kFloat8_e4m3fn) {
         hipLaunchKernelGGL(pi_hat_delta_kernel<__hip_fp8_e4m3>,
                            dim3(blocks), dim3(BLOCK), 0, stream.stream(),
@@ -2138,7 +2104,8 @@ torch::Tensor pi_hat_delta(torch::Tensor preds, torch::Tensor cls) {
                            cls.data_ptr<int>(), out.data_ptr<float>(),
                            H, N, C);
     } else {
-        TORCH_CHECK(false, "pi_hat_delta kernel supports fp32/bf16/fp8");
+        TORCH_CHECK(false,
+                    "pi_hat_delta kernel supports fp32/fp16/bf16/fp8");
     }
     C10_HIP_CHECK(hipGetLastError());
     return out;
@@ -2170,6 +2137,13 @@ torch::Tensor pi_hat_delta_part(torch::Tensor preds, torch::Tensor cls,
                                preds.data_ptr()),
                            cls.data_ptr<int>(), partial.data_ptr<float>(),
                            H, N, C, Hc);
+    } else if (preds.scalar_type() == torch::kFloat16) {
+        hipLaunchKernelGGL(pi_hat_delta_part_kernel<_Float16>,
+                           dim3(bx, KH), dim3(BLOCK), 0, stream.stream(),
+                           reinterpret_cast<const _Float16*>(
+                               preds.data_ptr()),
+                           cls.data_ptr<int>(), partial.data_ptr<float>(),
+                           H, N, C, Hc);
     } else if (preds.scalar_type() == torch::kFloat8_e4m3fn) {
         hipLaunchKernelGGL(pi_hat_delta_part_kernel<__hip_fp8_e4m3>,
                            dim3(bx, KH), dim3(BLOCK), 0, stream.stream(),
@@ -2178,7 +2152,8 @@ torch::Tensor pi_hat_delta_part(torch::Tensor preds, torch::Tensor cls,
                            cls.data_ptr<int>(), partial.data_ptr<float>(),
                            H, N, C, Hc);
     } else {
-        TORCH_CHECK(false, "pi_hat_delta kernel supports fp32/bf16/fp8");
+        TORCH_CHECK(false,
+                    "pi_hat_delta kernel supports fp32/fp16/bf16/fp8");
     }
     C10_HIP_CHECK(hipGetLastError());
     return partial;
@@ -2211,6 +2186,13 @@ torch::Tensor pi_hat_delta_t_part(torch::Tensor preds_t,
                                preds_t.data_ptr()),
                            cls.data_ptr<int>(), partial.data_ptr<float>(),
                            H, N, C, Hc);
+    } else if (preds_t.scalar_type() == torch::kFloat16) {
+        hipLaunchKernelGGL(pi_hat_delta_t_part_kernel<_Float16>,
+                           dim3(bx, KH), dim3(BLOCK), 0, stream.stream(),
+                           reinterpret_cast<const _Float16*>(
+                               preds_t.data_ptr()),
+                           cls.data_ptr<int>(), partial.data_ptr<float>(),
+                           H, N, C, Hc);
     } else if (preds_t.scalar_type() == torch::kFloat8_e4m3fn) {
         hipLaunchKernelGGL(pi_hat_delta_t_part_kernel<__hip_fp8_e4m3>,
                            dim3(bx, KH), dim3(BLOCK), 0, stream.stream(),
@@ -2219,7 +2201,8 @@ torch::Tensor pi_hat_delta_t_part(torch::Tensor preds_t,
                            cls.data_ptr<int>(), partial.data_ptr<float>(),
                            H, N, C, Hc);
     } else {
-        TORCH_CHECK(false, "pi_hat_delta kernel supports fp32/bf16/fp8");
+        TORCH_CHECK(false,
+                    "pi_hat_delta kernel supports fp32/fp16/bf16/fp8");
     }
     C10_HIP_CHECK(hipGetLastError());
     return partial;
@@ -2315,15 +2298,28 @@ torch::Tensor pi_marginal(torch::Tensor adjusted, torch::Tensor row_sums) {
         C10_HIP_CHECK(hipGetLastError());
         return out;
     }
-    auto out = torch::zeros({C}, adjusted.options());
-    const int blocks = 1536;  // 6 blocks/CU: enough row-slabs in flight
-                              // to cover HBM latency (512 ran at 1 TB/s)
-    hipLaunchKernelGGL(pi_marginal_kernel, dim3(blocks), dim3(BLOCK), 0,
+    // every other C: scalar slab partials + the same fixed-order reduce,
+    // on columns padded to a multiple of 4
+    const int Cpad = (C + 3) & ~3;
+    const int G = 1536;  // 6 blocks/CU: enough row-slabs in flight
+                         // to cover HBM latency (512 ran at 1 TB/s)
+    constexpr int S = 16;
+    auto out = torch::empty({Cpad}, adjusted.options());
+    auto work = torch::empty({G + S, Cpad}, adjusted.options());
+    float* partial = work.data_ptr<float>();
+    float* part2 = partial + (long long)G * Cpad;
+    const int cblocks = (Cpad + 4 * BLOCK - 1) / (4 * BLOCK);
+    hipLaunchKernelGGL(pi_marginal_kernel, dim3(G), dim3(BLOCK), 0,
                        stream.stream(), adjusted.data_ptr<float>(),
-                       row_sums.data_ptr<float>(), out.data_ptr<float>(),
-                       N, C);
+                       row_sums.data_ptr<float>(), partial, N, C, Cpad);
+    hipLaunchKernelGGL(pi_marginal_reduce_kernel, dim3(cblocks, S),
+                       dim3(BLOCK), 0, stream.stream(), partial, part2,
+                       G, Cpad, Cpad, Cpad);
+    hipLaunchKernelGGL(pi_marginal_reduce_kernel, dim3(cblocks, 1),
+                       dim3(BLOCK), 0, stream.stream(), part2,
+                       out.data_ptr<float>(), S, Cpad, Cpad, Cpad);
     C10_HIP_CHECK(hipGetLastError());
-    return out;
+    return out.narrow(0, 0, C);
 }
 
 void register_pair_ops(pybind11::module_& m);  // pair.hip (v3 engine)

@@ -49,7 +49,8 @@ def consensus(preds: torch.Tensor) -> torch.Tensor:
 def init_model_stats(preds: torch.Tensor, chunk_h: int = 0):
     """One chunked fp32-upcast pass over the model axis at selector init:
     cached argmax classes (H, N) + the consensus sum (N, C) fp32.
-    Storage may be fp32 / bf16 / fp8 (coda_amd.datasets.STORAGE_DTYPES);
+    Storage may be fp32 / fp16 / bf16 / fp8
+    (coda_amd.datasets.STORAGE_DTYPES);
     compute is always fp32. chunk_h defaults to <= 1 GiB of fp32 chunk
     (a fixed 16 was a 64 GB transient at the 1M-point config)."""
     H, N, C = preds.shape
@@ -63,6 +64,26 @@ def init_model_stats(preds: torch.Tensor, chunk_h: int = 0):
         classes[h0:h1] = ch.argmax(-1)
         ens += ch.sum(0)
     return classes, ens
+
+
+def ensemble_mean(preds: torch.Tensor, chunk_n: int = 0) -> torch.Tensor:
+    """Mean over the model axis, (H, N, C) -> (N, C), as the baselines'
+    surrogate takes it: in the pool's own dtype - except for an fp16 pool,
+    which is up-cast to fp32 first (exact), in point-axis chunks of
+    chunk_n points (default: <= 1 GiB of fp32). Every output element keeps the whole-tensor
+    reduction over h, so the result is `preds.float().mean(0)`: fp16
+    storage of an fp16-representable pool gives the fp32 run's surrogate
+    without a full fp32 copy."""
+    if preds.dtype != torch.float16:
+        return preds.mean(dim=0)
+    H, N, C = preds.shape
+    if chunk_n <= 0:
+        chunk_n = max(1, (1 << 28) // max(1, H * C))
+    out = torch.empty(N, C, dtype=torch.float32, device=preds.device)
+    for n0 in range(0, N, chunk_n):
+        n1 = min(n0 + chunk_n, N)
+        out[n0:n1] = preds[:, n0:n1].float().mean(dim=0)
+    return out
 
 
 def ingest_chunk(wire: torch.Tensor, h0: int, n0: int,

@@ -95,9 +95,10 @@ def parse_args(argv=None):
     parser.add_argument("--sharded", action="store_true",
                         help="Shard the model axis across torchrun ranks.")
     parser.add_argument("--storage", default="fp32",
-                        choices=["fp32", "bf16", "fp8"],
+                        choices=["fp32", "fp16", "bf16", "fp8"],
                         help="On-device prediction-pool dtype (compute "
-                             "always upcasts to fp32).")
+                             "always upcasts to fp32). fp16 is lossless "
+                             "for fp16 source data at half of fp32.")
     parser.add_argument("--stream-chunk-mb", type=int, default=0,
                         help="Stream the pool host->HBM through pinned "
                              "buffers of this size (0 = one blocking copy; "

@@ -2,12 +2,13 @@
 
 The benchmark .pt files ship fp16/fp32; storing bf16 or fp8-e4m3 halves /
 quarters both disk and host->device wire bytes (the loader up-casts to
-fp32 for compute either way - coda_amd/datasets.py). Labels files are
-copied unchanged.
+fp32 for compute either way - coda_amd/datasets.py); fp16 halves an fp32
+file and is lossless for data that was fp16 to begin with. Labels files
+are copied unchanged.
 
 Usage:
     python scripts/convert_task.py --task T [--data-dir data]
-        [--dtype bf16|fp8] [--out-dir data_bf16]
+        [--dtype fp16|bf16|fp8] [--out-dir data_bf16]
     python scripts/convert_task.py --all --data-dir data --dtype fp8
     python scripts/convert_task.py --task T --dtype fp8 --shards
         [--models-per-shard 16]

@@ -132,8 +132,12 @@ def main():
         "wall_s": {r: sorted(v) for r, v in times.items()},
         "wall_s_median": {r: sorted(v)[len(v) // 2]
                           for r, v in times.items() if v},
-        # legacy up-casts on the host and ships fp32; shards ship the file
-        "host_wire_bytes": {"legacy": elems * 4, "shards": elems * wsz},
+        # legacy up-casts on the host and ships fp32 (an fp16 file bound
+        # for fp16 storage ships as it is); shards ship the file
+        "host_wire_bytes": {
+            "legacy": elems * (2 if args.dtype == args.storage == "fp16"
+                               else 4),
+            "shards": elems * wsz},
         # wire in + pool out + mirror out + one consensus RMW per call
         "ingest_kernel_floor_bytes":
             elems * (wsz + 2 * ssz) + n_calls * 2 * N * C * 4,
