@@ -1534,6 +1534,20 @@ pi_marginal_reduce_kernel(const float* __restrict__ in,   // (G, Cpad)
 // Host bindings
 // ---------------------------------------------------------------------------
 
+// cls of the v2 assemble kernels: (B, H) int32 next to m (C, B, 2H)
+static void check_cls_for_m(const torch::Tensor& m,
+                            const torch::Tensor& cls) {
+    TORCH_CHECK(m.dim() == 3 && m.size(2) % 2 == 0, "m must be (C, B, 2H)");
+    TORCH_CHECK(m.scalar_type() == torch::kFloat32 ||
+                m.scalar_type() == torch::kBFloat16,
+                "m must be fp32 or bf16");
+    TORCH_CHECK(cls.is_cuda() && cls.is_contiguous(),
+                "cls must be contiguous on a ROCm device");
+    TORCH_CHECK(cls.scalar_type() == torch::kInt32, "cls must be int32");
+    TORCH_CHECK(cls.dim() == 2 && cls.size(0) == m.size(1) &&
+                cls.size(1) == m.size(2) / 2, "cls must be (B, H)");
+}
+
 static void check_f32_cuda(const torch::Tensor& t, const char* name) {
     TORCH_CHECK(t.is_cuda(), name, " must be on a ROCm device");
     TORCH_CHECK(t.scalar_type() == torch::kFloat32, name, " must be fp32");
@@ -1773,9 +1787,23 @@ torch::Tensor es_build(torch::Tensor s_base, torch::Tensor delta,
     TORCH_CHECK(hvals.scalar_type() == torch::kInt32 &&
                 offsets.scalar_type() == torch::kInt32,
                 "hvals/offsets must be int32");
-    TORCH_CHECK(s_base.size(1) == P_POINTS, "P must be 256");
+    TORCH_CHECK(s_base.dim() == 2 && s_base.size(1) == P_POINTS,
+                "P must be 256");
+    TORCH_CHECK(delta.dim() == 3 && delta.size(2) == P_POINTS,
+                "delta must be (C, H, 256)");
+    TORCH_CHECK(hvals.is_cuda() && hvals.is_contiguous() &&
+                offsets.is_cuda() && offsets.is_contiguous() &&
+                hvals.dim() == 2 && offsets.dim() == 2,
+                "hvals/offsets must be contiguous 2-d device tensors");
     const int C = s_base.size(0), H = delta.size(1);
     const int B = hvals.size(0);
+    TORCH_CHECK(delta.size(0) == C, "delta.size(0) must equal C");
+    TORCH_CHECK(dall.dim() == 2 && dall.size(0) == C &&
+                dall.size(1) == P_POINTS, "dall must be (C, 256)");
+    TORCH_CHECK(hvals.size(1) == H, "hvals must be (B, H)");
+    TORCH_CHECK(offsets.size(0) == B && offsets.size(1) == C + 1,
+                "offsets must be (B, C+1)");
+    TORCH_CHECK(w.numel() == P_POINTS, "w must be (256,)");
     auto es = torch::empty({C, B, P_POINTS},
                            s_base.options().dtype(
                                bf16_out ? torch::kBFloat16
@@ -1840,7 +1868,7 @@ torch::Tensor eig_assemble_k(torch::Tensor m, torch::Tensor cls,
     check_f32_cuda(pi_hat, "pi_hat");
     check_f32_cuda(pbest_before, "pbest_before");
     check_f32_cuda(mixture0, "mixture0");
-    TORCH_CHECK(cls.scalar_type() == torch::kInt32, "cls must be int32");
+    check_cls_for_m(m, cls);
     const int C = m.size(0), B = m.size(1);
     const int H = m.size(2) / 2;
     auto h_after = torch::empty({B, C},
@@ -1881,8 +1909,20 @@ torch::Tensor es_build_gathered(torch::Tensor s_base_all,
     TORCH_CHECK(hvals.scalar_type() == torch::kInt32 &&
                 offsets.scalar_type() == torch::kInt32,
                 "hvals/offsets must be int32");
+    TORCH_CHECK(s_base_all.dim() == 2 && s_base_all.size(1) == P_POINTS,
+                "P must be 256");
+    TORCH_CHECK(hvals.is_cuda() && hvals.is_contiguous() &&
+                offsets.is_cuda() && offsets.is_contiguous() &&
+                hvals.dim() == 2 && offsets.dim() == 2,
+                "hvals/offsets must be contiguous 2-d device tensors");
     const int C = s_base_all.size(0);
     const int B = hvals.size(0), Hg = hvals.size(1);
+    TORCH_CHECK(sel_all.dim() == 3 && sel_all.size(0) == B &&
+                sel_all.size(1) == Hg && sel_all.size(2) == P_POINTS,
+                "sel_all must be (B, Hg, 256)");
+    TORCH_CHECK(offsets.size(0) == B && offsets.size(1) == C + 1,
+                "offsets must be (B, C+1)");
+    TORCH_CHECK(w.numel() == P_POINTS, "w must be (256,)");
     auto es = torch::empty({C, B, P_POINTS},
                            s_base_all.options().dtype(
                                bf16_out ? torch::kBFloat16
@@ -1914,6 +1954,7 @@ torch::Tensor es_build_gathered(torch::Tensor s_base_all,
 
 torch::Tensor eig_totals(torch::Tensor m, torch::Tensor cls) {
     TORCH_CHECK(m.is_cuda() && m.is_contiguous(), "m");
+    check_cls_for_m(m, cls);
     const int C = m.size(0), B = m.size(1), H = m.size(2) / 2;
     auto totals = torch::empty({B, C},
                                m.options().dtype(torch::kFloat32));
@@ -1942,8 +1983,16 @@ torch::Tensor eig_entropy(torch::Tensor m, torch::Tensor cls,
                           torch::Tensor pbest_before,
                           torch::Tensor mixture0) {
     TORCH_CHECK(m.is_cuda() && m.is_contiguous(), "m");
+    check_cls_for_m(m, cls);
     check_f32_cuda(totals, "totals");
+    check_f32_cuda(pi_hat, "pi_hat");
+    check_f32_cuda(pbest_before, "pbest_before");
+    check_f32_cuda(mixture0, "mixture0");
     const int C = m.size(0), B = m.size(1), H = m.size(2) / 2;
+    TORCH_CHECK(totals.numel() == (int64_t)B * C, "totals must be (B, C)");
+    TORCH_CHECK(pi_hat.numel() == C && mixture0.numel() == H &&
+                pbest_before.numel() == (int64_t)C * H,
+                "pi_hat (C,), pbest_before (C, H), mixture0 (H,)");
     auto h_after = torch::empty({B, C},
                                 m.options().dtype(torch::kFloat32));
     const int R = B * C;
