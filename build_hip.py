@@ -18,7 +18,8 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 SRC = [os.path.join(REPO, "coda_amd", "ops", "hip", "pbest.hip"),
        os.path.join(REPO, "coda_amd", "ops", "hip", "pair.hip"),
        os.path.join(REPO, "coda_amd", "ops", "hip", "ingest.hip"),
-       os.path.join(REPO, "coda_amd", "ops", "hip", "ingest_f16.hip")]
+       os.path.join(REPO, "coda_amd", "ops", "hip", "ingest_f16.hip"),
+       os.path.join(REPO, "coda_amd", "ops", "hip", "modelpicker.hip")]
 # headers the sources include: part of the up-to-date check only
 HDR = [os.path.join(REPO, "coda_amd", "ops", "hip", "ingest_kernel.h")]
 OUT = os.path.join(REPO, "coda_amd", "ops",

@@ -68,6 +68,8 @@ def load_state_dict(selector, state: Dict[str, Any]):
             from sortedcontainers import SortedList
             v = SortedList(v)
         setattr(selector, f, v)
+    if cls == "ModelPicker" and selector.entropy_impl == "sparse":
+        selector._rebuild_unlabeled_mask()   # mirrors d_u_idxs on device
     # derived state that depends on the posterior
     if cls == "CODA":
         selector._tables = None       # force a fresh v2 table build

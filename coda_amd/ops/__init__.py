@@ -29,6 +29,8 @@ from .reference import (  # re-export cheap ops + constants
     mixture_entropy as _mixture_entropy_eager,
     pred_classes, disagreement_mask,
     accuracy_losses, entropy_acquisition, vma_pairwise, lure_weights,
+    MODELPICKER_MAX_H, MODELPICKER_MAX_C, ModelPickerStruct,
+    modelpicker_build, modelpicker_prologue,
 )
 
 _ext = None
@@ -80,6 +82,21 @@ def ingest_chunk(wire: torch.Tensor, h0: int, n0: int,
         return
     reference.ingest_chunk(wire, h0, n0, preds_out, classes_out, ens_out,
                            preds_t_out)
+
+
+def modelpicker_dev(struct: ModelPickerStruct, posterior: torch.Tensor,
+                    gamma: float, active: torch.Tensor) -> torch.Tensor:
+    """Hit-sparse ModelPicker entropy deviation per point: (N,) fp32,
+    +inf where active[n] == 0 (contract: reference.modelpicker_dev). On a
+    ROCm device this is one gfx950 launch (modelpicker.hip), a wave per
+    point over the static (N, H) int16 structure, with fixed-order sums."""
+    if _want_hip(struct.packed):
+        p, q = reference.modelpicker_prologue(posterior)
+        if active.dtype == torch.bool:
+            active = active.view(torch.uint8)
+        return _ext.modelpicker_dev(struct.packed, p, q, float(gamma),
+                                    active.contiguous())
+    return reference.modelpicker_dev(struct, posterior, gamma, active)
 
 
 def pbest_from_beta(alpha: torch.Tensor, beta: torch.Tensor,

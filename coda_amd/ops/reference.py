@@ -450,3 +450,110 @@ def lure_weights(qs: torch.Tensor, N: int) -> torch.Tensor:
     M = qs.shape[0]
     m = torch.arange(1, M + 1, device=qs.device, dtype=qs.dtype)
     return 1.0 + ((N - M) / (N - m)) * (1.0 / ((N - m + 1.0) * qs) - 1.0)
+
+
+# ---------------------------------------------------------------------------
+# Hit-sparse ModelPicker entropy (contract of ops/hip/modelpicker.hip)
+# ---------------------------------------------------------------------------
+
+MODELPICKER_MAX_H = 1024      # 16 sorted positions per lane of a wave64
+MODELPICKER_MAX_C = 32767     # classes are sorted as int16
+
+
+class ModelPickerStruct:
+    """Static hit structure of a pool's argmax classes.
+
+    packed (N, H) int16: per point the models sorted by predicted class
+    (stable: ties keep ascending model index). Bits 0..14 are the model
+    index, bit 15 marks a position whose class differs from the previous
+    position's (position 0 carries no mark), so every class's model set
+    is a contiguous segment in a fixed order. nseg (N,) int32 is the
+    number of distinct classes per point.
+    """
+
+    def __init__(self, packed: torch.Tensor, nseg: torch.Tensor):
+        self.packed = packed
+        self.nseg = nseg
+        self.N, self.H = packed.shape
+
+
+def modelpicker_build(classes_nh: torch.Tensor,
+                      chunk: int = 65536) -> ModelPickerStruct:
+    """(N, H) integer argmax classes -> ModelPickerStruct, chunked over
+    points so the int64 sort transients stay O(chunk x H)."""
+    N, H = classes_nh.shape
+    if H < 1 or H > MODELPICKER_MAX_H:
+        raise ValueError(f"hit-sparse ModelPicker supports 1 <= H <= "
+                         f"{MODELPICKER_MAX_H} models, got {H}")
+    packed = torch.empty(N, H, dtype=torch.int16, device=classes_nh.device)
+    nseg = torch.empty(N, dtype=torch.int32, device=classes_nh.device)
+    for n0 in range(0, N, chunk):
+        cls = classes_nh[n0:n0 + chunk]
+        if cls.numel() and (int(cls.min()) < 0
+                            or int(cls.max()) >= MODELPICKER_MAX_C):
+            raise ValueError("hit-sparse ModelPicker supports class ids in "
+                             f"[0, {MODELPICKER_MAX_C})")
+        cls_sorted, order = torch.sort(cls, dim=1, stable=True)
+        head = torch.zeros_like(cls_sorted, dtype=torch.bool)
+        head[:, 1:] = cls_sorted[:, 1:] != cls_sorted[:, :-1]
+        mark = torch.where(head, -32768, 0).to(torch.int16)
+        packed[n0:n0 + chunk] = order.to(torch.int16) | mark
+        nseg[n0:n0 + chunk] = head.sum(dim=1, dtype=torch.int32) + 1
+    return ModelPickerStruct(packed, nseg)
+
+
+def modelpicker_prologue(posterior: torch.Tensor):
+    """The (H,) inputs of the closed form, shared by the kernel and its
+    eager twin: p_h = post_h / sum(post) and the centred
+    q_h = p_h (log2 p_h + E0) with E0 = -sum_h p_h log2 p_h (0 log 0 = 0).
+
+    Evaluated in fp64 and rounded once: for the models A predicting a
+    class the closed form needs S E0 + T (S = sum_A p_h, T = sum_A p_h
+    log2 p_h), two terms that nearly cancel - exactly for a uniform
+    posterior - and move the result by (g-1) times any error in E0; the
+    sum of q_h over A is that quantity without the cancellation."""
+    p = posterior.double()
+    p = p / p.sum()
+    lp = torch.log2(torch.where(p > 0, p, torch.ones_like(p)))
+    e0 = -(p * lp).sum()
+    q = torch.where(p > 0, p * (lp + e0), torch.zeros_like(p))
+    return p.float().contiguous(), q.float().contiguous()
+
+
+def modelpicker_dev(struct: ModelPickerStruct, posterior: torch.Tensor,
+                    gamma: float, active: torch.Tensor,
+                    chunk: int = 8192) -> torch.Tensor:
+    """dev[n] = sum over the distinct classes c hit on point n of
+    (ent_c - E0), +inf where active[n] == 0. With S and T' the sums of the
+    prologue's p_h and q_h over the models predicting c,
+
+        ent_c - E0 = log2(1 + (g-1) S)
+                     - [(g-1) T' + g log2(g) S] / (1 + (g-1) S)
+
+    and a point on which all models agree gets exactly 0. Vectorised over
+    the static segments, never more than O(chunk x H) live.
+    """
+    import math
+    p, q = modelpicker_prologue(posterior)
+    gm1 = float(gamma) - 1.0
+    glg = float(gamma) * math.log2(float(gamma))
+    N, H = struct.N, struct.H
+    out = torch.empty(N, dtype=torch.float32, device=p.device)
+    pos = torch.arange(H, device=p.device)
+    for n0 in range(0, N, chunk):
+        pk = struct.packed[n0:n0 + chunk].to(torch.int64)
+        seg = torch.cumsum((pk < 0).to(torch.int64), dim=1)   # (c, H)
+        m = pk & 0x7fff
+        S = torch.zeros(pk.shape, dtype=torch.float32, device=p.device)
+        T = torch.zeros_like(S)
+        S.scatter_add_(1, seg, p[m])
+        T.scatter_add_(1, seg, q[m])
+        nseg = struct.nseg[n0:n0 + chunk].to(torch.int64).unsqueeze(1)
+        x = gm1 * S
+        term = (torch.log1p(x) * (1.0 / math.log(2.0))
+                - (gm1 * T + glg * S) / (1.0 + x))
+        live = (pos.unsqueeze(0) < nseg) & (nseg > 1)
+        out[n0:n0 + chunk] = torch.where(live, term,
+                                         torch.zeros_like(term)).sum(dim=1)
+    return torch.where(active.to(torch.bool), out,
+                       torch.full_like(out, float("inf")))

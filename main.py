@@ -103,6 +103,12 @@ def parse_args(argv=None):
                         help="Stream the pool host->HBM through pinned "
                              "buffers of this size (0 = one blocking copy; "
                              "sharded tasks always stream, 256 when 0).")
+    parser.add_argument("--mp-entropy", default="auto",
+                        choices=["auto", "dense", "sparse"],
+                        help="ModelPicker expected-entropy path: the dense "
+                             "(Nu, C, H) expression, the hit-sparse HIP "
+                             "kernel over the whole pool, or 'auto' (sparse "
+                             "on GPU once a dense temporary reaches 1 GiB).")
     parser.add_argument("--checkpoint-every", type=int, default=0,
                         help="Save selector state every K steps (0 = off); "
                              "an interrupted seed resumes mid-run.")
@@ -134,6 +140,7 @@ def build_selector(dataset, args, loss_fn, comm=None):
         # per-task epsilon: the built-in table, overridden by a tuned
         # best_epsilons.json (scripts/modelpicker_eps_gridsearch.py)
         eps = TASK_EPS.get(args.task)
+        mp_entropy = getattr(args, "mp_entropy", "auto")
         import json
         for cand in ("best_epsilons.json",
                      os.path.join(args.data_dir, "best_epsilons.json")):
@@ -146,8 +153,8 @@ def build_selector(dataset, args, loss_fn, comm=None):
                     pass
         if eps is None:
             print(args.task, "not in TASK_EPS; using default")
-            return ModelPicker(dataset)
-        return ModelPicker(dataset, epsilon=eps)
+            return ModelPicker(dataset, entropy_impl=mp_entropy)
+        return ModelPicker(dataset, epsilon=eps, entropy_impl=mp_entropy)
     raise ValueError(args.method + " is not a supported method.")
 
 
