@@ -1554,6 +1554,44 @@ static void check_f32_cuda(const torch::Tensor& t, const char* name) {
     TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
 
+// (R, H) Beta rows of the v1 phase kernels
+static void check_beta_rows(const torch::Tensor& alpha,
+                            const torch::Tensor& beta) {
+    check_f32_cuda(alpha, "alpha");
+    check_f32_cuda(beta, "beta");
+    TORCH_CHECK(alpha.dim() == 2 && alpha.sizes() == beta.sizes(),
+                "alpha/beta must be (R, H)");
+}
+
+// the H-coupling term a phase-2 kernel reads: one 256-point row per
+// P(best) row
+static void check_slog2(const torch::Tensor& slog2, int64_t rows) {
+    check_f32_cuda(slog2, "slog2");
+    TORCH_CHECK(slog2.dim() == 2 && slog2.size(0) == rows &&
+                slog2.size(1) == P_POINTS,
+                "slog2 must be (R, 256), R = ", rows);
+}
+
+// (H, C) diagonal Betas + the (B, H) int32 argmax classes of the v1 EIG
+// kernels (stage_hyp indexes cls[b * H + h] and alpha_t[c * H + h])
+static void check_hyp_inputs(const torch::Tensor& alpha_cc,
+                             const torch::Tensor& beta_cc,
+                             const torch::Tensor& cls) {
+    TORCH_CHECK(alpha_cc.is_cuda() && beta_cc.is_cuda(),
+                "alpha_cc/beta_cc must be on a ROCm device");
+    TORCH_CHECK(alpha_cc.scalar_type() == torch::kFloat32 &&
+                beta_cc.scalar_type() == torch::kFloat32,
+                "alpha_cc/beta_cc must be fp32");
+    TORCH_CHECK(alpha_cc.dim() == 2 && alpha_cc.sizes() == beta_cc.sizes(),
+                "alpha_cc/beta_cc must be (H, C)");
+    TORCH_CHECK(cls.is_cuda() && cls.is_contiguous(),
+                "chunk_classes must be contiguous on a ROCm device");
+    TORCH_CHECK(cls.scalar_type() == torch::kInt32,
+                "chunk_classes must be int32");
+    TORCH_CHECK(cls.dim() == 2 && cls.size(1) == alpha_cc.size(0),
+                "chunk_classes must be (B, H)");
+}
+
 torch::Tensor pbest_from_beta(torch::Tensor alpha, torch::Tensor beta,
                               int64_t num_points) {
     check_f32_cuda(alpha, "alpha");
@@ -1600,12 +1638,17 @@ torch::Tensor eig_chunk(torch::Tensor alpha_cc, torch::Tensor beta_cc,
     check_f32_cuda(pi_hat, "pi_hat");
     check_f32_cuda(pi_hat_xi, "pi_hat_xi");
     check_f32_cuda(mixture0, "mixture0");
-    TORCH_CHECK(chunk_classes.scalar_type() == torch::kInt32,
-                "chunk_classes must be int32");
+    check_hyp_inputs(alpha_cc, beta_cc, chunk_classes);
     TORCH_CHECK(num_points == P_POINTS,
                 "HIP eig kernel is compiled for P=256");
     const int H = alpha_cc.size(0), C = alpha_cc.size(1);
     const int B = chunk_classes.size(0);
+    TORCH_CHECK(pbest_before.dim() == 2 && pbest_before.size(0) == C &&
+                pbest_before.size(1) == H, "pbest_before must be (C, H)");
+    TORCH_CHECK(pi_hat.numel() == C, "pi_hat must be (C,)");
+    TORCH_CHECK(mixture0.numel() == H, "mixture0 must be (H,)");
+    TORCH_CHECK(pi_hat_xi.dim() == 2 && pi_hat_xi.size(0) == B &&
+                pi_hat_xi.size(1) == C, "pi_hat_xi must be (B, C)");
     // (H, C) -> (C, H) contiguous rows for per-class streaming
     auto alpha_t = alpha_cc.t().contiguous();
     auto beta_t = beta_cc.t().contiguous();
@@ -1635,8 +1678,7 @@ torch::Tensor eig_chunk(torch::Tensor alpha_cc, torch::Tensor beta_cc,
 // ---- Two-phase (sharded) host bindings ----
 
 torch::Tensor pbest_phase1(torch::Tensor alpha, torch::Tensor beta) {
-    check_f32_cuda(alpha, "alpha");
-    check_f32_cuda(beta, "beta");
+    check_beta_rows(alpha, beta);
     const int R = alpha.size(0), H = alpha.size(1);
     auto slog2 = torch::empty({R, P_POINTS}, alpha.options());
     if (R == 0) return slog2;
@@ -1655,14 +1697,14 @@ torch::Tensor pbest_phase1(torch::Tensor alpha, torch::Tensor beta) {
 std::vector<torch::Tensor> pbest_phase2(torch::Tensor alpha,
                                         torch::Tensor beta,
                                         torch::Tensor slog2) {
-    check_f32_cuda(alpha, "alpha");
-    check_f32_cuda(beta, "beta");
-    check_f32_cuda(slog2, "slog2");
+    check_beta_rows(alpha, beta);
+    check_slog2(slog2, alpha.size(0));
     const int R = alpha.size(0), H = alpha.size(1);
     auto pb = torch::empty({R, H}, alpha.options());
     auto tot = torch::empty({R}, alpha.options());
     if (R == 0) return {pb, tot};
     const size_t smem = lds_bytes(H);
+    TORCH_CHECK(smem <= 160 * 1024, "H too large for LDS: ", H);
     const int blocks = (R + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
     auto stream = c10::hip::getCurrentHIPStream();
     hipLaunchKernelGGL(pbest_phase2_kernel, dim3(blocks), dim3(BLOCK), smem,
@@ -1675,8 +1717,8 @@ std::vector<torch::Tensor> pbest_phase2(torch::Tensor alpha,
 
 torch::Tensor pbest_phase1_wide(torch::Tensor alpha, torch::Tensor beta,
                                 int64_t hc) {
-    check_f32_cuda(alpha, "alpha");
-    check_f32_cuda(beta, "beta");
+    check_beta_rows(alpha, beta);
+    TORCH_CHECK(hc >= 1, "hc must be >= 1");
     const int R = alpha.size(0), Htot = alpha.size(1);
     const int Hc = std::min<int64_t>(hc, Htot);
     const int KH = (Htot + Hc - 1) / Hc;
@@ -1698,9 +1740,9 @@ std::vector<torch::Tensor> pbest_phase2_wide(torch::Tensor alpha,
                                              torch::Tensor beta,
                                              torch::Tensor slog2,
                                              int64_t hc) {
-    check_f32_cuda(alpha, "alpha");
-    check_f32_cuda(beta, "beta");
-    check_f32_cuda(slog2, "slog2");
+    check_beta_rows(alpha, beta);
+    check_slog2(slog2, alpha.size(0));
+    TORCH_CHECK(hc >= 1, "hc must be >= 1");
     const int R = alpha.size(0), Htot = alpha.size(1);
     const int Hc = std::min<int64_t>(hc, Htot);
     const int KH = (Htot + Hc - 1) / Hc;
@@ -1722,13 +1764,11 @@ std::vector<torch::Tensor> pbest_phase2_wide(torch::Tensor alpha,
 
 torch::Tensor eig_phase1(torch::Tensor alpha_cc, torch::Tensor beta_cc,
                          torch::Tensor chunk_classes, double update_weight) {
+    check_hyp_inputs(alpha_cc, beta_cc, chunk_classes);
     const int H = alpha_cc.size(0), C = alpha_cc.size(1);
     const int B = chunk_classes.size(0);
     auto alpha_t = alpha_cc.t().contiguous();
     auto beta_t = beta_cc.t().contiguous();
-    check_f32_cuda(alpha_t, "alpha_cc");
-    TORCH_CHECK(chunk_classes.scalar_type() == torch::kInt32,
-                "chunk_classes must be int32");
     auto slog2 = torch::empty({(int64_t)B * C, P_POINTS}, alpha_t.options());
     const size_t smem = lds_bytes(H);
     TORCH_CHECK(smem <= 160 * 1024, "H too large for LDS: ", H);
@@ -1750,15 +1790,16 @@ std::vector<torch::Tensor> eig_phase2(torch::Tensor alpha_cc,
                                       torch::Tensor chunk_classes,
                                       torch::Tensor slog2,
                                       double update_weight) {
+    check_hyp_inputs(alpha_cc, beta_cc, chunk_classes);
     const int H = alpha_cc.size(0), C = alpha_cc.size(1);
     const int B = chunk_classes.size(0);
+    check_slog2(slog2, (int64_t)B * C);
     auto alpha_t = alpha_cc.t().contiguous();
     auto beta_t = beta_cc.t().contiguous();
-    check_f32_cuda(alpha_t, "alpha_cc");
-    check_f32_cuda(slog2, "slog2");
     auto pb = torch::empty({(int64_t)B * C, H}, alpha_t.options());
     auto tot = torch::empty({(int64_t)B * C}, alpha_t.options());
     const size_t smem = lds_bytes(H);
+    TORCH_CHECK(smem <= 160 * 1024, "H too large for LDS: ", H);
     const int R = B * C;
     const int blocks = (R + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
     auto stream = c10::hip::getCurrentHIPStream();

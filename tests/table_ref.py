@@ -234,16 +234,34 @@ def ref_beta_row_curves(alpha_col, beta_col, update_weight, *, f32=False,
     Faults: swap_v exchanges the two variants; lane0_trapezoid counts a
     first trapezoid 0.5 (pdf[0] + pdf[3]) dx at lane 0 (what the
     shuffle hands lane 0 without the guard)."""
-    lx, l1mx, lx0, l1mx0, dlx, dl1mx, dxf = _grid()
     uw = torch.tensor(float(update_weight), dtype=torch.float32)
     al, be = alpha_col.float(), beta_col.float()
-    a = torch.stack([al, al + uw], -1).double().unsqueeze(-1)   # (H,2,1)
-    b = torch.stack([be + uw, be], -1).double().unsqueeze(-1)
+    a = torch.stack([al, al + uw], -1)                          # (H, 2)
+    b = torch.stack([be + uw, be], -1)
     if swap_v:
         a, b = a.flip(1), b.flip(1)
+    t2, _, cdf = curves(a, b, f32, lane0_trapezoid=lane0_trapezoid)
+    eps = _f32c(1e-30, torch.float64)
+    if not f32:
+        lc = torch.log2(cdf.clamp_min(eps))
+        return torch.exp2(t2 - lc), lc
+    lc = _r32(torch.log2(cdf.clamp_min(eps)))
+    return _r32(torch.exp2(_r32(t2 - lc))), lc
+
+
+def curves(a, b, f32=False, *, lane0_trapezoid=False):
+    """(t2, pdf, cdf), each (..., P) fp64, of the Beta(a, b) curves on
+    the grid; a and b are fp32 tensors of one shape (the kernels'
+    operands). t2 = base-2 log-pdf, pdf = 2^t2, cdf = trapezoid-
+    cumulative pdf with the fp32 step and cdf[..., 0] = 0. f32 follows
+    LaneGrid::pdf4 / cdf4 operation by operation (see
+    ref_beta_row_curves, and tests/pbest_ref.py for the v1 kernels that
+    share it)."""
+    lx, l1mx, lx0, l1mx0, dlx, dl1mx, dxf = _grid()
+    a = a.float().double().unsqueeze(-1)
+    b = b.float().double().unsqueeze(-1)
     lnB2 = (torch.lgamma(a) + torch.lgamma(b) - torch.lgamma(a + b)) * LOG2E
     am1, bm1 = a - 1.0, b - 1.0
-    eps = _f32c(1e-30, torch.float64)
     if not f32:
         t2 = am1 * lx + bm1 * l1mx - lnB2
         pdf = torch.exp2(t2)
@@ -252,8 +270,7 @@ def ref_beta_row_curves(alpha_col, beta_col, update_weight, *, f32=False,
         if lane0_trapezoid:
             first = 0.5 * (pdf[..., 0:1] + pdf[..., 3:4]) * dxf
         cdf = torch.cumsum(torch.cat([first, tr], -1), -1)
-        lc = torch.log2(cdf.clamp_min(eps))
-        return torch.exp2(t2 - lc), lc
+        return t2, pdf, cdf
     K = _r32(am1 * lx0 + bm1 * l1mx0 - lnB2)
     t2 = _r32(am1 * dlx + _r32(bm1 * dl1mx + K))
     pdf = _r32(torch.exp2(t2))
@@ -270,8 +287,7 @@ def ref_beta_row_curves(alpha_col, beta_col, update_weight, *, f32=False,
     c2 = _r32(c1 + tr[..., 2])
     c3 = _r32(c2 + tr[..., 3])
     cdf = torch.stack([c0, c1, c2, c3], -1).reshape(pdf.shape)
-    lc = _r32(torch.log2(cdf.clamp_min(eps)))
-    return _r32(torch.exp2(_r32(t2 - lc))), lc
+    return t2, pdf, cdf
 
 
 class CommitRow(NamedTuple):
