@@ -82,6 +82,7 @@ def load_state_dict(selector, state: Dict[str, Any]):
         selector._acq_fresh = False
         selector._acq_saved = None
         selector._merged_acq = False
+        selector._drop_pair_cache()    # built from the replaced tables
         selector._pairs_static = None  # hit structure covers a stale set
         selector._pair_row_of = None
         selector._active_mask = None

@@ -33,6 +33,15 @@
 //                          h_base), in a fixed lane-strided order
 //                          (deterministic - no atomics).
 //
+// Pair cache (fused 128-pair route with a static structure): a label
+// rewrites ONE class's table rows, and everything up to a pair's
+// selected pairing masses and their normalizer depends only on its own
+// class's rows. pair_gemm_pbn128_kernel keeps those in a persistent
+// (K, H) fp32 cache; per step pair_dsum_es_cls_kernel +
+// pair_gemm_pbn128_kernel refresh the labelled class's run of pairs and
+// pair_entropy_cached_kernel streams the cache into h_after, replacing
+// the full dsum + GEMM over all K pairs with bit-identical results.
+//
 // MFMA: v_mfma_f32_16x16x32_bf16. Lane mapping (cdna_hip_programming.md
 // section 3): A[i][k] i=lane&15, k=(lane>>4)*8+e; B[k][j] j=lane&15,
 // same k; C/D col=lane&15, row=(lane>>4)*4+reg. The B operand is stored
@@ -87,20 +96,21 @@ __device__ __forceinline__ float wave_reduce(float v) {
 // ---------------------------------------------------------------------
 // A-operand build: a16[k, p] = 2^(sum_{h in seg(k)} delta16[c_k, h, p])
 // ---------------------------------------------------------------------
-__global__ void __launch_bounds__(BLOCK)
-pair_dsum_es_kernel(const _Float16* __restrict__ delta16,  // (C, H, P)
-                    const float* __restrict__ dall,        // (C, P)
-                    const int* __restrict__ pair_c,        // (K,)
-                    const int* __restrict__ pair_neg,      // (K,)
-                    const int* __restrict__ seg_off,       // (K+1,)
-                    const int* __restrict__ seg_h,         // (S,)
-                    hip_bfloat16* __restrict__ a16,        // (K, P)
-                    int K, int H) {
+// One pair's row, by the 16 lanes that own it: pair k of the structure,
+// written to a16 row `arow` (k itself for the full operand, k minus the
+// class's run start for the one-class scratch operand).
+__device__ __forceinline__ void
+dsum_es_row(const _Float16* __restrict__ delta16,  // (C, H, P)
+            const float* __restrict__ dall,        // (C, P)
+            const int* __restrict__ pair_c,        // (K,)
+            const int* __restrict__ pair_neg,      // (K,)
+            const int* __restrict__ seg_off,       // (K+1,)
+            const int* __restrict__ seg_h,         // (S,)
+            hip_bfloat16* __restrict__ a16,
+            int k, int arow, int H) {
     // 16 lanes per pair (the hit distribution is singleton-heavy:
     // avg segment ~2 models - a wave per pair would mostly idle on one
     // 512-B load). Each lane owns 16 grid points as 4x half4v loads.
-    const int k = blockIdx.x * 16 + (threadIdx.x >> 4);
-    if (k >= K) return;
     const int sublane = threadIdx.x & 15;
     const int p0 = sublane * 16;
     const int c = pair_c[k];
@@ -171,8 +181,47 @@ pair_dsum_es_kernel(const _Float16* __restrict__ delta16,  // (C, H, P)
     for (int j = 0; j < 16; ++j)
         o[j] = hip_bfloat16(exp2f(acc[j])).data;
     ushort4* dst = reinterpret_cast<ushort4*>(
-        a16 + (size_t)k * P_POINTS + p0);
+        a16 + (size_t)arow * P_POINTS + p0);
     dst[0] = out[0]; dst[1] = out[1]; dst[2] = out[2]; dst[3] = out[3];
+}
+
+__global__ void __launch_bounds__(BLOCK)
+pair_dsum_es_kernel(const _Float16* __restrict__ delta16,  // (C, H, P)
+                    const float* __restrict__ dall,        // (C, P)
+                    const int* __restrict__ pair_c,        // (K,)
+                    const int* __restrict__ pair_neg,      // (K,)
+                    const int* __restrict__ seg_off,       // (K+1,)
+                    const int* __restrict__ seg_h,         // (S,)
+                    hip_bfloat16* __restrict__ a16,        // (K, P)
+                    int K, int H) {
+    const int k = blockIdx.x * 16 + (threadIdx.x >> 4);
+    if (k >= K) return;
+    dsum_es_row(delta16, dall, pair_c, pair_neg, seg_off, seg_h, a16,
+                k, k, H);
+}
+
+// One class's run of pairs [run_off[y], run_off[y+1]) with the class id
+// read on the device (the label graph's y_t), into the (max_run, P)
+// scratch operand indexed from the run start. The grid covers the
+// longest run of any class; the rest return.
+__global__ void __launch_bounds__(BLOCK)
+pair_dsum_es_cls_kernel(const _Float16* __restrict__ delta16,
+                        const float* __restrict__ dall,
+                        const int* __restrict__ pair_c,
+                        const int* __restrict__ pair_neg,
+                        const int* __restrict__ seg_off,
+                        const int* __restrict__ seg_h,
+                        const int* __restrict__ run_off,    // (C+1,)
+                        const long long* __restrict__ y_t,  // (1,)
+                        hip_bfloat16* __restrict__ a_run,   // (max_run, P)
+                        int max_run, int C, int H) {
+    const long long y = y_t[0];
+    if (y < 0 || y >= C) return;
+    const int rel = blockIdx.x * 16 + (threadIdx.x >> 4);
+    const int k = run_off[y] + rel;
+    if (rel >= max_run || k >= run_off[y + 1]) return;
+    dsum_es_row(delta16, dall, pair_c, pair_neg, seg_off, seg_h, a_run,
+                k, rel, H);
 }
 
 // ---------------------------------------------------------------------
@@ -297,6 +346,23 @@ __device__ __forceinline__ float row16_reduce(float v) {
     return __shfl(v, 15, 16);    // broadcast row total to all 16 lanes
 }
 
+// One selected column's entropy term, added to the lane's running sum:
+// pb = m * inv (the pair's normalized P(best) for model h), mm =
+// max(mix + pic * (pb - pbb), 1e-12), ent - mm * log2(mm). The fused
+// epilogue and the cached pass below both inline THIS function, so the
+// compiler contracts it the same way in both (as it always has in the
+// fused kernel: fma(m, inv, -pbb), fma(pic, ., mix), fma(-mm, log2 mm,
+// ent) - pb is never rounded on its own, which is why the cache keeps m
+// and inv apart). tests/test_pair_cache_gpu.py holds the two kernels to
+// bit equality.
+__device__ __forceinline__ void pair_ent_acc(float& ent, float mix,
+                                             float pic, float m,
+                                             float inv, float pbb) {
+    const float pb = m * inv;
+    const float mm = fmaxf(mix + pic * (pb - pbb), 1e-12f);
+    ent += -mm * __log2f(mm);
+}
+
 template <int JT>
 __global__ void __launch_bounds__(BLOCK2)
 pair_gemm_entropy128_kernel(const hip_bfloat16* __restrict__ a16,
@@ -405,11 +471,8 @@ pair_gemm_entropy128_kernel(const hip_bfloat16* __restrict__ a16,
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int bit = (vmw[r][jt >> 2] >> (h & 31)) & 1;
-            if (bit == v) {
-                const float pb = acc[jt][r] * inv[r];
-                const float mm = fmaxf(mix + pic * (pb - pbb), 1e-12f);
-                ent[r] += -mm * __log2f(mm);
-            }
+            if (bit == v)
+                pair_ent_acc(ent[r], mix, pic, acc[jt][r], inv[r], pbb);
         }
     }
 #pragma unroll
@@ -419,6 +482,234 @@ pair_gemm_entropy128_kernel(const hip_bfloat16* __restrict__ a16,
     }
     }  // tile loop
     (void)mstride;
+}
+
+
+// Pair-cache build/refresh: pair_gemm_entropy128_kernel's B stage, MFMA
+// loop, vmask select and tot reduction, with the entropy epilogue
+// replaced by a store of what depends only on the class's own table
+// rows - the selected accumulators pm[k, h] and the pair's inv[k] - to
+// the persistent cache; pair_entropy_cached_kernel finishes from them.
+// (A sibling, not a shared inlined body: wrapping the fused kernel's
+// body in a device function changed its code generation - 24 more
+// VGPRs and a spill at JT = 17.)
+// y_t == nullptr: block b takes group b (the one-off full build over
+// the full (K, P) operand). Otherwise the class id is read on the
+// device and block b takes group cls_grp_off[y] + b, reading the
+// one-class scratch operand, whose row 0 is structure row run_off[y];
+// the grid is the largest group count of any class, and a block past
+// the class's range returns - the whole block takes that branch, before
+// the first __syncthreads(). Class y's groups cover rows [run_off[y],
+// run_off[y+1]) exactly, so a refresh writes those cache rows and no
+// others.
+template <int JT>
+__global__ void __launch_bounds__(BLOCK2)
+pair_gemm_pbn128_kernel(const hip_bfloat16* __restrict__ a16,
+                        const hip_bfloat16* __restrict__ egw,
+                        const unsigned* __restrict__ vmask,
+                        const int* __restrict__ pair_c,
+                        int W,
+                        const int* __restrict__ grp_off,      // (G+1,)
+                        const int* __restrict__ cls_grp_off,  // (C+1,)
+                        const int* __restrict__ run_off,      // (C+1,)
+                        const long long* __restrict__ y_t,    // (1,)
+                        float* __restrict__ pm,               // (K, H)
+                        float* __restrict__ pinv,             // (K,)
+                        int C, int H) {
+    int g = blockIdx.x, a_row0 = 0;
+    if (y_t != nullptr) {
+        const long long y = y_t[0];
+        if (y < 0 || y >= C) return;
+        g += cls_grp_off[y];
+        if (g >= cls_grp_off[y + 1]) return;
+        a_row0 = run_off[y];
+    }
+    extern __shared__ char smem[];
+    const int twoH = 2 * H;
+    hip_bfloat16* b_lds = reinterpret_cast<hip_bfloat16*>(smem);
+
+    const int t0 = grp_off[g], t1 = grp_off[g + 1];
+    const int c = pair_c[t0 * 128];
+    const int tid = threadIdx.x;
+    const int wave = tid >> 6, lane = tid & 63;
+    const int row16 = lane & 15;
+    const int kgrp = lane >> 4;
+    const hip_bfloat16* egw_c = egw + (size_t)c * twoH * P_POINTS;
+
+    // stage the whole B table: row j (512 B) split in 2 halves; thread
+    // t copies half (t&1) of row (t>>1) - fully coalesced 16-B loads
+    for (int t = tid; t < 2 * twoH; t += BLOCK2) {
+        const int j = t >> 1, half = t & 1;
+        const uint4* g = reinterpret_cast<const uint4*>(
+            egw_c + (size_t)j * P_POINTS + half * 128);
+        uint4* d = reinterpret_cast<uint4*>(
+            reinterpret_cast<char*>(b_lds)
+            + (size_t)j * BSTRIDE * 2 + half * 256);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) d[i] = g[i];
+    }
+    __syncthreads();
+
+    for (int tile = t0; tile < t1; ++tile) {
+    const int k0 = tile * 128;
+    f32x4 acc[JT];
+#pragma unroll
+    for (int jt = 0; jt < JT; ++jt) acc[jt] = {0.f, 0.f, 0.f, 0.f};
+
+    const hip_bfloat16* arow =
+        a16 + (size_t)(k0 - a_row0 + wave * 16 + row16) * P_POINTS;
+#pragma unroll
+    for (int kk = 0; kk < P_POINTS; kk += 32) {
+        const bf16x8 afrag = *reinterpret_cast<const bf16x8*>(
+            arow + kk + kgrp * 8);
+#pragma unroll
+        for (int jt = 0; jt < JT; ++jt) {
+            const int j = jt * 16 + row16;
+            bf16x8 bfrag = {};
+            if (j < twoH)
+                bfrag = *reinterpret_cast<const bf16x8*>(
+                    b_lds + (size_t)j * BSTRIDE + kk + kgrp * 8);
+            acc[jt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                afrag, bfrag, acc[jt], 0, 0, 0);
+        }
+    }
+
+    // register-resident epilogue: lane owns pairs kbase..kbase+3 (the
+    // accumulator rows) at columns jt*16+row16. For column j: h = j>>1
+    // and it contributes to pair r iff vmask bit h == (j&1).
+    const int kbase = k0 + wave * 16 + kgrp * 4;
+    unsigned vmw[4][(JT + 3) / 4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int w = 0; w < (JT + 3) / 4; ++w)
+            vmw[r][w] = (w < W)
+                ? vmask[(size_t)(kbase + r) * W + w] : 0u;
+
+    float tot[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int jt = 0; jt < JT; ++jt) {
+        const int j = jt * 16 + row16;
+        if (j >= twoH) continue;
+        const int h = j >> 1, v = j & 1;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int bit = (vmw[r][jt >> 2] >> (h & 31)) & 1;
+            if (bit == v) tot[r] += acc[jt][r];
+        }
+    }
+    float inv[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        inv[r] = 1.0f / fmaxf(row16_reduce(tot[r]), 1e-30f);
+
+    // lanes 2m and 2m+1 hold the two variants of model h = j >> 1; the
+    // vmask bit picks the one that writes pm[k, h]
+#pragma unroll
+    for (int jt = 0; jt < JT; ++jt) {
+        const int j = jt * 16 + row16;
+        if (j >= twoH) continue;
+        const int h = j >> 1, v = j & 1;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int bit = (vmw[r][jt >> 2] >> (h & 31)) & 1;
+            if (bit == v) pm[(size_t)(kbase + r) * H + h] = acc[jt][r];
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        if (row16 == 0) pinv[kbase + r] = inv[r];
+    }  // tile loop
+}
+
+
+// ---------------------------------------------------------------------
+// Per-step pass over the pair cache: h_after[k] from pm[k, :], inv[k]
+// and the quantities that move every step (pi_hat, mixture0, one row of
+// pbest_before). Sixteen lanes per pair in the fused kernel's order:
+// lane l walks jt ascending with column j = jt*16 + l (h = j >> 1,
+// v = j & 1), adds the term iff vmask bit h == v, then the same
+// row16_reduce - bit-identical to pair_gemm_entropy128_kernel.
+// A chunk's 16 rows are one contiguous 16*H-float span (runs are
+// 128-padded, so a chunk never straddles classes): staged through LDS
+// with float4 loads, with the class's pbest_before row and mixture0.
+// ---------------------------------------------------------------------
+#define ECH 4   // 16-pair chunks per block (K % 128 == 0 => K % 64 == 0)
+
+__global__ void __launch_bounds__(BLOCK)
+pair_entropy_cached_kernel(const float* __restrict__ pm,      // (K, H)
+                           const float* __restrict__ pinv,    // (K,)
+                           const unsigned* __restrict__ vmask,
+                           const int* __restrict__ pair_c,
+                           int W,
+                           const float* __restrict__ pi_hat,
+                           const float* __restrict__ pbest_before,
+                           const float* __restrict__ mixture0,
+                           float* __restrict__ h_after,       // (K,)
+                           int H) {
+    extern __shared__ char smem[];
+    float* rows = reinterpret_cast<float*>(smem);   // [16 * H]
+    float* mix_s = rows + 16 * H;                   // [H]
+    float* pbb_s = mix_s + H;                       // [H]
+
+    // the block walks ECH consecutive 16-pair chunks (64 pairs: inside
+    // one 128-pair tile, so one class); chunk i+1's rows are in flight
+    // in registers while chunk i is evaluated from LDS
+    const int kb = blockIdx.x * (16 * ECH);
+    const int c = pair_c[kb];
+    const int tid = threadIdx.x;
+    const int nv4 = 4 * H;      // float4 per chunk: 16*H floats, <= 544
+    // chunk start kb + 16*ch: (kb + 16*ch)*H*4 bytes, 64-B aligned
+    const f32x4* g = reinterpret_cast<const f32x4*>(pm + (size_t)kb * H);
+    // (native vectors: an array of HIP's float4 struct stays in scratch)
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 nxt[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q)
+        nxt[q] = tid + q * BLOCK < nv4 ? g[tid + q * BLOCK] : zero4;
+    for (int h = tid; h < H; h += BLOCK) {
+        mix_s[h] = mixture0[h];
+        pbb_s[h] = pbest_before[(size_t)c * H + h];
+    }
+    const int pi = tid >> 4, l = tid & 15;
+    const float pic = pi_hat[c];
+    const float* row = rows + pi * H;
+    const int twoH = 2 * H;
+    const int JT = (twoH + 15) / 16;
+
+#pragma unroll
+    for (int ch = 0; ch < ECH; ++ch) {
+        f32x4* d = reinterpret_cast<f32x4*>(rows);
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+            if (tid + q * BLOCK < nv4) d[tid + q * BLOCK] = nxt[q];
+        __syncthreads();
+        if (ch + 1 < ECH) {
+            const f32x4* gn = g + (size_t)(ch + 1) * nv4;
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+                nxt[q] = tid + q * BLOCK < nv4 ? gn[tid + q * BLOCK]
+                                               : zero4;
+        }
+        const int k = kb + ch * 16 + pi;
+        const float inv = pinv[k];
+        float ent = 0.f;
+        unsigned vw = 0u;
+        for (int jt = 0; jt < JT; ++jt) {
+            const int j = jt * 16 + l;
+            // h >> 5 == jt >> 2 for every column of this sweep
+            if ((jt & 3) == 0)
+                vw = (jt >> 2) < W ? vmask[(size_t)k * W + (jt >> 2)] : 0u;
+            if (j >= twoH) continue;
+            const int h = j >> 1, v = j & 1;
+            const int bit = (vw >> (h & 31)) & 1;
+            if (bit == v)
+                pair_ent_acc(ent, mix_s[h], pic, row[h], inv, pbb_s[h]);
+        }
+        const float e = row16_reduce(ent);
+        if (l == 0) h_after[k] = e;
+        __syncthreads();     // rows are overwritten by the next chunk
+    }
 }
 
 // ---------------------------------------------------------------------
@@ -922,6 +1213,158 @@ torch::Tensor pair_gemm_entropy(torch::Tensor a16, torch::Tensor egw,
     return h_after;
 }
 
+// -- pair cache (fused B-resident route only: tile 128, 2H <= 272) -----
+
+void pair_dsum_es_cls(torch::Tensor delta16, torch::Tensor dall,
+                      torch::Tensor pair_c, torch::Tensor pair_neg,
+                      torch::Tensor seg_off, torch::Tensor seg_h,
+                      torch::Tensor run_off, torch::Tensor y_t,
+                      torch::Tensor a_run) {
+    TORCH_CHECK(delta16.is_cuda() && delta16.dtype() == torch::kFloat16);
+    TORCH_CHECK(delta16.size(-1) == P_POINTS);
+    TORCH_CHECK(dall.dtype() == torch::kFloat32);
+    TORCH_CHECK(a_run.dtype() == torch::kBFloat16 && a_run.is_contiguous()
+                && a_run.dim() == 2 && a_run.size(1) == P_POINTS,
+                "a_run must be a contiguous (max_run, P) bf16 scratch");
+    TORCH_CHECK(y_t.is_cuda() && y_t.scalar_type() == torch::kInt64
+                && y_t.numel() == 1, "y_t must be a (1,) int64 tensor");
+    const int C = delta16.size(0);
+    const int H = delta16.size(1);
+    TORCH_CHECK(run_off.scalar_type() == torch::kInt32
+                && run_off.is_contiguous() && run_off.numel() == C + 1,
+                "run_off must be (C+1,) int32");
+    const int max_run = a_run.size(0);
+    if (max_run == 0) return;
+    auto stream = c10::hip::getCurrentHIPStream();
+    hipLaunchKernelGGL(pairops::pair_dsum_es_cls_kernel,
+                       dim3((max_run + 15) / 16), dim3(BLOCK), 0,
+                       stream.stream(),
+                       reinterpret_cast<const _Float16*>(
+                           delta16.data_ptr()),
+                       dall.data_ptr<float>(),
+                       pair_c.data_ptr<int>(), pair_neg.data_ptr<int>(),
+                       seg_off.data_ptr<int>(), seg_h.data_ptr<int>(),
+                       run_off.data_ptr<int>(),
+                       reinterpret_cast<const long long*>(
+                           y_t.data_ptr<int64_t>()),
+                       reinterpret_cast<hip_bfloat16*>(a_run.data_ptr()),
+                       max_run, C, H);
+}
+
+// y_t absent: all groups from the full (K, P) operand a16.
+// Otherwise class y_t[0]'s groups from the one-class scratch operand
+// (a16 = a_run), on a grid of max_grp blocks.
+void pair_gemm_pbn(torch::Tensor a16, torch::Tensor egw,
+                   torch::Tensor vmask, torch::Tensor pair_c,
+                   torch::Tensor grp, torch::Tensor pm,
+                   torch::Tensor pinv,
+                   c10::optional<torch::Tensor> cls_grp_off_o,
+                   c10::optional<torch::Tensor> run_off_o,
+                   c10::optional<torch::Tensor> y_t_o,
+                   int64_t max_grp) {
+    TORCH_CHECK(a16.is_cuda() && a16.dtype() == torch::kBFloat16
+                && a16.is_contiguous() && a16.size(1) == P_POINTS);
+    TORCH_CHECK(egw.dtype() == torch::kBFloat16 && egw.is_contiguous());
+    TORCH_CHECK(pm.dtype() == torch::kFloat32 && pm.is_contiguous()
+                && pm.dim() == 2, "pm must be contiguous (K, H) fp32");
+    const int K = pm.size(0);
+    const int H = pm.size(1);
+    const int C = egw.size(0);
+    TORCH_CHECK(pinv.dtype() == torch::kFloat32 && pinv.is_contiguous()
+                && pinv.numel() == K, "pinv must be (K,) fp32");
+    TORCH_CHECK(K % 128 == 0 && pair_c.numel() == K
+                && vmask.size(0) == K, "pair cache needs 128-pair tiles");
+    TORCH_CHECK(egw.size(1) == 2 * H && 2 * H <= 272,
+                "pair cache covers the fused route only (2H <= 272)");
+    TORCH_CHECK(grp.scalar_type() == torch::kInt32 && grp.is_contiguous()
+                && grp.numel() >= 2, "grp must be the (G+1,) tile groups");
+    const bool one_class = y_t_o.has_value();
+    int nblk = grp.numel() - 1;
+    const int* cgo = nullptr;
+    const int* roff = nullptr;
+    const long long* yp = nullptr;
+    if (one_class) {
+        TORCH_CHECK(cls_grp_off_o.has_value() && run_off_o.has_value(),
+                    "one-class mode needs cls_grp_off and run_off");
+        const torch::Tensor& y_t = *y_t_o;
+        const torch::Tensor& cls_grp_off = *cls_grp_off_o;
+        const torch::Tensor& run_off = *run_off_o;
+        TORCH_CHECK(y_t.is_cuda() && y_t.scalar_type() == torch::kInt64
+                    && y_t.numel() == 1, "y_t must be a (1,) int64 tensor");
+        TORCH_CHECK(cls_grp_off.scalar_type() == torch::kInt32
+                    && cls_grp_off.is_contiguous()
+                    && cls_grp_off.numel() == C + 1
+                    && run_off.scalar_type() == torch::kInt32
+                    && run_off.is_contiguous()
+                    && run_off.numel() == C + 1,
+                    "cls_grp_off / run_off must be (C+1,) int32");
+        TORCH_CHECK(max_grp >= 1 && max_grp <= nblk);
+        nblk = (int)max_grp;
+        cgo = cls_grp_off.data_ptr<int>();
+        roff = run_off.data_ptr<int>();
+        yp = reinterpret_cast<const long long*>(y_t.data_ptr<int64_t>());
+    } else {
+        TORCH_CHECK(a16.size(0) == K, "full build needs the (K, P) operand");
+    }
+    const size_t shmem = (size_t)2 * H * BSTRIDE * sizeof(hip_bfloat16);
+    const int JT = (2 * H + 15) / 16;
+    auto stream = c10::hip::getCurrentHIPStream();
+    auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(nblk), dim3(BLOCK2), shmem,
+                           stream.stream(),
+                           reinterpret_cast<const hip_bfloat16*>(
+                               a16.data_ptr()),
+                           reinterpret_cast<const hip_bfloat16*>(
+                               egw.data_ptr()),
+                           reinterpret_cast<const unsigned*>(
+                               vmask.data_ptr<int>()),
+                           pair_c.data_ptr<int>(), (int)vmask.size(1),
+                           grp.data_ptr<int>(), cgo, roff, yp,
+                           pm.data_ptr<float>(), pinv.data_ptr<float>(),
+                           C, H);
+    };
+    if (JT <= 4) launch(pairops::pair_gemm_pbn128_kernel<4>);
+    else if (JT <= 8) launch(pairops::pair_gemm_pbn128_kernel<8>);
+    else if (JT <= 16) launch(pairops::pair_gemm_pbn128_kernel<16>);
+    else launch(pairops::pair_gemm_pbn128_kernel<17>);
+}
+
+torch::Tensor pair_entropy_cached(torch::Tensor pm, torch::Tensor pinv,
+                                  torch::Tensor vmask,
+                                  torch::Tensor pair_c,
+                                  torch::Tensor pi_hat,
+                                  torch::Tensor pbest_before,
+                                  torch::Tensor mixture0) {
+    TORCH_CHECK(pm.is_cuda() && pm.dtype() == torch::kFloat32
+                && pm.is_contiguous() && pm.dim() == 2);
+    const int K = pm.size(0);
+    const int H = pm.size(1);
+    TORCH_CHECK(K % 128 == 0 && 2 * H <= 272,
+                "pair cache covers the fused route only");
+    TORCH_CHECK(pinv.is_contiguous() && pinv.numel() == K
+                && pair_c.numel() == K && vmask.size(0) == K);
+    TORCH_CHECK(mixture0.numel() == H && mixture0.is_contiguous()
+                && pbest_before.is_contiguous()
+                && pbest_before.size(1) == H
+                && pi_hat.is_contiguous());
+    auto h_after = torch::empty({K}, pi_hat.options());
+    if (K == 0) return h_after;
+    const size_t shmem = (size_t)18 * H * sizeof(float);
+    auto stream = c10::hip::getCurrentHIPStream();
+    hipLaunchKernelGGL(pairops::pair_entropy_cached_kernel,
+                       dim3(K / (16 * ECH)), dim3(BLOCK), shmem,
+                       stream.stream(),
+                       pm.data_ptr<float>(), pinv.data_ptr<float>(),
+                       reinterpret_cast<const unsigned*>(
+                           vmask.data_ptr<int>()),
+                       pair_c.data_ptr<int>(), (int)vmask.size(1),
+                       pi_hat.data_ptr<float>(),
+                       pbest_before.data_ptr<float>(),
+                       mixture0.data_ptr<float>(),
+                       h_after.data_ptr<float>(), H);
+    return h_after;
+}
+
 torch::Tensor pair_eig_finalize(torch::Tensor h_after,
                                 torch::Tensor h_base,
                                 torch::Tensor pair_c,
@@ -1061,6 +1504,23 @@ void register_pair_ops(pybind11::module_& m) {
           pybind11::arg("grp") = torch::Tensor());
     m.def("pair_gemm_entropy_cls", &pair_gemm_entropy_cls,
           "v3 wide-H pairing GEMM + cls-based entropy -> (K,)");
+    m.def("pair_dsum_es_cls", &pair_dsum_es_cls,
+          "pair A-operand of ONE class (id read on device) into the "
+          "(max_run, P) scratch operand");
+    m.def("pair_gemm_pbn", &pair_gemm_pbn,
+          "pair-cache build (all groups) / one-class refresh: selected "
+          "pairing masses pm (K, H) and inv (K,)",
+          pybind11::arg("a16"), pybind11::arg("egw"),
+          pybind11::arg("vmask"), pybind11::arg("pair_c"),
+          pybind11::arg("grp"), pybind11::arg("pm"),
+          pybind11::arg("pinv"),
+          pybind11::arg("cls_grp_off") = pybind11::none(),
+          pybind11::arg("run_off") = pybind11::none(),
+          pybind11::arg("y_t") = pybind11::none(),
+          pybind11::arg("max_grp") = 0);
+    m.def("pair_entropy_cached", &pair_entropy_cached,
+          "per-step entropy pass over the pair cache -> (K,), bit-equal "
+          "to the fused 128-pair kernel");
     m.def("pair_eig_finalize", &pair_eig_finalize,
           "v3 per-candidate EIG assembly (deterministic) -> (B,)");
     m.def("acq_select", &acq_select,

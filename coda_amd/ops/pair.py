@@ -97,6 +97,17 @@ class PairStructure(NamedTuple):
     # class's tiles instead of re-staging per tile (classes average
     # ~2.4 tiles at the headline distribution)
     grp_off: torch.Tensor = None
+    # -- per-class views for the pair cache's one-class refresh (built
+    # with grp_off, i.e. for 128-pair tiles) --
+    # (C+1,) int32 — class c's tile groups are grp_off entries
+    # [cls_grp_off[c], cls_grp_off[c+1]) (groups are class-uniform and
+    # class-ordered)
+    cls_grp_off: torch.Tensor = None
+    # (C+1,) int32 — class c's run of pairs is [run_off[c], run_off[c+1])
+    # (run_off[:-1] == base_pos, run_off[-1] == K)
+    run_off: torch.Tensor = None
+    max_grp: int = 0         # most tile groups of any class
+    max_run: int = 0         # longest class run, in pairs
 
     @property
     def K(self) -> int:
@@ -270,8 +281,19 @@ def build_pairs(cls_rows: torch.Tensor, cand_ids: torch.Tensor,
             idx[gstart].to(torch.int32),
             torch.tensor([T], dtype=torch.int32, device=device),
         ]).contiguous()
+        # a class owns at least its base pair's tile, hence >= 1 group
+        grp_per_cls = torch.bincount(tc[gstart].long(), minlength=C)
+        cls_grp_off = torch.zeros(C + 1, dtype=torch.int32, device=device)
+        cls_grp_off[1:] = grp_per_cls.cumsum(0).to(torch.int32)
+        per_class = dict(cls_grp_off=cls_grp_off,
+                         run_off=run_off.to(torch.int32),
+                         max_grp=int(grp_per_cls.max()),
+                         max_run=int(run_len.max()))
+    else:
+        per_class = {}
 
-    return PairStructure(cand_ids=cand_ids.long().contiguous(),
+    return PairStructure(**per_class,
+                         cand_ids=cand_ids.long().contiguous(),
                          pair_b=pair_b,
                          pair_c=pair_c, seg_off=seg_off, seg_h=seg_h,
                          base_pos=run_off[:-1].clone(), n_real=K2,
@@ -284,6 +306,66 @@ def build_pairs(cls_rows: torch.Tensor, cand_ids: torch.Tensor,
                          else None)
 
 
+def pair_pbn(tables, ps: PairStructure, cls_rows: torch.Tensor,
+             k0: int = 0, k1: Optional[int] = None) -> torch.Tensor:
+    """(k1-k0, H) normalized hypothetical P(best) of pairs [k0, k1)
+    (default: all K), eager formulation.
+
+    Row k depends only on class pair_c[k]'s table rows and the static
+    hit structure - the part of h_after a label on another class leaves
+    untouched (what the pair cache keeps). The (K, 2H, P) gather makes
+    it unusable at headline scale on purpose.
+    """
+    EG, delta, s_base, w = (tables.EG, tables.delta, tables.s_base,
+                            tables.weights)
+    C, H, _, P = EG.shape
+    k1 = ps.K if k1 is None else k1
+    K = k1 - k0
+    device = EG.device
+
+    seg_off = ps.seg_off[k0:k1 + 1]
+    seg_h = ps.seg_h[int(seg_off[0]):int(seg_off[-1])] if K else ps.seg_h[:0]
+    pair_b = ps.pair_b[k0:k1]
+    seg_len = (seg_off[1:] - seg_off[:-1]).long()
+    seg_pair = torch.repeat_interleave(
+        torch.arange(K, device=device), seg_len)
+    pc_long = ps.pair_c[k0:k1].long()
+    dsum = torch.zeros(K, P, device=device)
+    if seg_h.numel():
+        dsum.index_add_(0, seg_pair,
+                        delta[pc_long[seg_pair], seg_h.long()])
+    pair_neg = None if ps.pair_neg is None else ps.pair_neg[k0:k1]
+    if pair_neg is not None and bool(pair_neg.any()):
+        dall = tables.dall if getattr(tables, "dall", None) is not None \
+            else delta.sum(1)
+        neg = pair_neg.bool()
+        dsum[neg] = dall[pc_long[neg]] - dsum[neg]
+    A = torch.exp2(dsum + s_base[pc_long]) * w              # (K, P)
+    M = torch.einsum('kp,kjp->kj', A,
+                     EG.reshape(C, 2 * H, P)[pc_long])      # (K, 2H)
+
+    b_safe = pair_b.long().clamp_min(0)
+    v = (cls_rows[b_safe] == pc_long.unsqueeze(1)) \
+        & (pair_b >= 0).unsqueeze(1)                        # (K, H)
+    j = 2 * torch.arange(H, device=device).unsqueeze(0) + v.long()
+    pb = M.gather(1, j)                                     # (K, H)
+    tot = pb.sum(-1, keepdim=True).clamp_min(EPS_PROB)
+    return pb / tot
+
+
+def h_after_from_pbn(pbn: torch.Tensor, ps: PairStructure,
+                     pi_hat: torch.Tensor, pbest_before: torch.Tensor,
+                     mixture0: torch.Tensor) -> torch.Tensor:
+    """(K,) hypothetical-update entropies from the (K, H) pair_pbn rows:
+    the only part that reads what moves everywhere each step (pi_hat,
+    mixture0, one row of pbest_before)."""
+    pc_long = ps.pair_c.long()
+    mm = (mixture0.unsqueeze(0)
+          + pi_hat[pc_long].unsqueeze(1)
+          * (pbn - pbest_before[pc_long])).clamp_min(1e-12)
+    return -(mm * torch.log2(mm)).sum(-1)                   # (K,)
+
+
 def pair_h_after(tables, ps: PairStructure, cls_rows: torch.Tensor,
                  pbest_before: torch.Tensor, pi_hat: torch.Tensor,
                  mixture0: torch.Tensor) -> torch.Tensor:
@@ -291,43 +373,122 @@ def pair_h_after(tables, ps: PairStructure, cls_rows: torch.Tensor,
 
     Math identical to ops/table.py's dense form restricted to hit cells
     (the kernel in ops/hip/pair.hip reproduces it in bf16-GEMM form).
-    Used on CPU and as the numerics reference for the kernel; the (K,
-    2H, P) gather makes it unusable at headline scale on purpose.
+    Used on CPU and as the numerics reference for the kernel.
     """
-    EG, delta, s_base, w = (tables.EG, tables.delta, tables.s_base,
-                            tables.weights)
-    C, H, _, P = EG.shape
-    K = ps.K
-    device = EG.device
+    return h_after_from_pbn(pair_pbn(tables, ps, cls_rows), ps, pi_hat,
+                            pbest_before, mixture0)
 
-    seg_len = (ps.seg_off[1:] - ps.seg_off[:-1]).long()
-    seg_pair = torch.repeat_interleave(
-        torch.arange(K, device=device), seg_len)
-    pc_long = ps.pair_c.long()
-    dsum = torch.zeros(K, P, device=device)
-    if ps.seg_h.numel():
-        dsum.index_add_(0, seg_pair,
-                        delta[pc_long[seg_pair], ps.seg_h.long()])
-    if ps.pair_neg is not None and bool(ps.pair_neg.any()):
-        dall = tables.dall if getattr(tables, "dall", None) is not None \
-            else delta.sum(1)
-        neg = ps.pair_neg.bool()
-        dsum[neg] = dall[pc_long[neg]] - dsum[neg]
-    A = torch.exp2(dsum + s_base[pc_long]) * w              # (K, P)
-    M = torch.einsum('kp,kjp->kj', A,
-                     EG.reshape(C, 2 * H, P)[pc_long])      # (K, 2H)
 
-    b_safe = ps.pair_b.long().clamp_min(0)
-    v = (cls_rows[b_safe] == pc_long.unsqueeze(1)) \
-        & (ps.pair_b >= 0).unsqueeze(1)                     # (K, H)
-    j = 2 * torch.arange(H, device=device).unsqueeze(0) + v.long()
-    pb = M.gather(1, j)                                     # (K, H)
-    tot = pb.sum(-1, keepdim=True).clamp_min(EPS_PROB)
-    pbn = pb / tot
-    mm = (mixture0.unsqueeze(0)
-          + pi_hat[pc_long].unsqueeze(1)
-          * (pbn - pbest_before[pc_long])).clamp_min(1e-12)
-    return -(mm * torch.log2(mm)).sum(-1)                   # (K,)
+# ---------------------------------------------------------------------
+# Pair cache: a label rewrites ONE class's table rows, so every other
+# class's pair_pbn rows carry over to the next step unchanged.
+# ---------------------------------------------------------------------
+
+class PairCache:
+    """Per-pair state that depends only on the pair's own class rows,
+    for one static structure.
+
+    Kernel form (GPU): `pm` (K, H) fp32 selected pairing masses and
+    `pinv` (K,) their normalizers 1/max(tot, 1e-30) - the pair's
+    normalized P(best) is pm * pinv, kept unmultiplied because the
+    fused kernel feeds the product into an fma without rounding it, and
+    the cached pass has to reproduce its bits - plus the persistent
+    one-class A operand `a_run` (max_run, P) bf16.
+    Eager form (CPU): `pbn` (K, H) = pair_pbn.
+    """
+
+    def __init__(self):
+        self.pm = self.pinv = self.a_run = self.pbn = None
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size()
+                   for t in (self.pm, self.pinv, self.a_run, self.pbn)
+                   if t is not None)
+
+
+def pair_cache_gate(tables, ps: PairStructure) -> bool:
+    """The structures the pair cache covers: the fused B-resident route
+    (128-pair tiles, 2H <= 272, vmask) with the per-class group views.
+    The caller adds the rest of the gate: the structure is the static
+    full-pool one and the cache fits in memory."""
+    H = tables.EG.shape[1]
+    return (ps.tile == 128 and 2 * H <= 272 and ps.vmask is not None
+            and ps.grp_off is not None and ps.cls_grp_off is not None)
+
+
+def pair_cache_bytes(ps: PairStructure, H: int) -> int:
+    """Bytes the cache holds (K*H*4 + K*4 + the one-class scratch) plus
+    the one-off build's temporary (K, P) bf16 operand."""
+    P = PBEST_NUM_POINTS
+    return ps.K * H * 4 + ps.K * 4 + ps.max_run * P * 2 + ps.K * P * 2
+
+
+def _kernel_form(tables) -> bool:
+    import coda_amd.ops as O
+    EG = tables.EG
+    return (EG.is_cuda and EG.shape[-1] == PBEST_NUM_POINTS
+            and getattr(tables, "egw", None) is not None
+            and O._want_hip(EG))
+
+
+def pair_cache_build(tables, ps: PairStructure,
+                     cls_rows: torch.Tensor) -> PairCache:
+    """Full build over all K pairs (one-off; not capturable: the (K, P)
+    operand is a temporary)."""
+    import coda_amd.ops as O
+    cache = PairCache()
+    H = tables.EG.shape[1]
+    if not _kernel_form(tables):
+        cache.pbn = pair_pbn(tables, ps, cls_rows)
+        return cache
+    dev = tables.EG.device
+    cache.pm = torch.zeros(ps.K, H, device=dev)
+    cache.pinv = torch.zeros(ps.K, device=dev)
+    cache.a_run = torch.zeros(ps.max_run, PBEST_NUM_POINTS,
+                              dtype=torch.bfloat16, device=dev)
+    A16 = O._ext.pair_dsum_es(tables.delta16, tables.dall, ps.pair_c,
+                              ps.pair_neg, ps.seg_off, ps.seg_h)
+    O._ext.pair_gemm_pbn(A16, tables.egw, ps.vmask, ps.pair_c,
+                         ps.grp_off, cache.pm, cache.pinv)
+    return cache
+
+
+def pair_cache_refresh(cache: PairCache, tables, ps: PairStructure,
+                       cls_rows: torch.Tensor, y) -> None:
+    """Recompute class y's rows [run_off[y], run_off[y+1]) after its
+    table rows changed; no other byte of the cache is written.
+
+    Kernel form: y is the (1,) int64 DEVICE tensor table_commit_row
+    takes - two static-grid launches, no host sync (graph-capturable).
+    Eager form: y is a python int.
+    """
+    if cache.pbn is not None:
+        y = int(y)
+        k0, k1 = int(ps.run_off[y]), int(ps.run_off[y + 1])
+        cache.pbn[k0:k1] = pair_pbn(tables, ps, cls_rows, k0, k1)
+        return
+    import coda_amd.ops as O
+    O._ext.pair_dsum_es_cls(tables.delta16, tables.dall, ps.pair_c,
+                            ps.pair_neg, ps.seg_off, ps.seg_h,
+                            ps.run_off, y, cache.a_run)
+    O._ext.pair_gemm_pbn(cache.a_run, tables.egw, ps.vmask, ps.pair_c,
+                         ps.grp_off, cache.pm, cache.pinv,
+                         ps.cls_grp_off, ps.run_off, y, ps.max_grp)
+
+
+def pair_cache_h_after(cache: PairCache, ps: PairStructure,
+                       pi_hat: torch.Tensor, pbest_before: torch.Tensor,
+                       mixture0: torch.Tensor) -> torch.Tensor:
+    """(K,) h_after from the cache: one streaming pass, bit-identical
+    to pair_dsum_es + pair_gemm_entropy on the same tables."""
+    if cache.pbn is not None:
+        return h_after_from_pbn(cache.pbn, ps, pi_hat, pbest_before,
+                                mixture0)
+    import coda_amd.ops as O
+    return O._ext.pair_entropy_cached(
+        cache.pm, cache.pinv, ps.vmask, ps.pair_c, pi_hat.contiguous(),
+        pbest_before.contiguous(), mixture0.contiguous())
 
 
 def eig_from_pairs(h_after: torch.Tensor, ps: PairStructure,
@@ -353,15 +514,38 @@ def eig_from_pairs(h_after: torch.Tensor, ps: PairStructure,
     return H_before - base_n - corr
 
 
+def _h_after_kernels(tables, ps: PairStructure, cls_rows, pbest_before,
+                     pi_hat, mixture0) -> torch.Tensor:
+    """(K,) h_after through pair_dsum_es + the route's GEMM kernel."""
+    import coda_amd.ops as O
+    A16 = O._ext.pair_dsum_es(tables.delta16, tables.dall,
+                              ps.pair_c, ps.pair_neg, ps.seg_off,
+                              ps.seg_h)                     # (K, P) bf16
+    if ps.vmask is None:
+        return O._ext.pair_gemm_entropy_cls(
+            A16, tables.egw, ps.pair_b, ps.pair_c,
+            cls_rows.to(torch.int32).contiguous(),
+            pi_hat.contiguous(), pbest_before.contiguous(),
+            mixture0.contiguous())                          # (K,)
+    grp = (ps.grp_off if ps.grp_off is not None
+           else torch.empty(0, dtype=torch.int32, device=A16.device))
+    return O._ext.pair_gemm_entropy(
+        A16, tables.egw, ps.vmask, ps.pair_c,
+        pi_hat.contiguous(), pbest_before.contiguous(),
+        mixture0.contiguous(), ps.tile, 0, grp)             # (K,)
+
+
 def eig_pairs(tables, ps: PairStructure, cls_rows: torch.Tensor,
               pbest_before: torch.Tensor, pi_hat: torch.Tensor,
               mixture0: torch.Tensor, H_before,
               adjusted: torch.Tensor,
-              row_sums: torch.Tensor) -> torch.Tensor:
+              row_sums: torch.Tensor,
+              h_after: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Full v3 EIG: (B,) values, one per structure candidate row.
 
     Dispatches the per-pair work to the HIP kernels when available
-    (GPU), else the eager formulation.
+    (GPU), else the eager formulation. h_after: the (K,) per-pair
+    entropies when the caller already has them (pair_cache_h_after).
     """
     import coda_amd.ops as O
     EG = tables.EG
@@ -369,23 +553,9 @@ def eig_pairs(tables, ps: PairStructure, cls_rows: torch.Tensor,
     if (EG.is_cuda and P == PBEST_NUM_POINTS
             and getattr(tables, "egw", None) is not None
             and O._want_hip(EG)):
-        A16 = O._ext.pair_dsum_es(tables.delta16, tables.dall,
-                                  ps.pair_c, ps.pair_neg, ps.seg_off,
-                                  ps.seg_h)                 # (K, P) bf16
-        if ps.vmask is None:
-            h_after = O._ext.pair_gemm_entropy_cls(
-                A16, tables.egw, ps.pair_b, ps.pair_c,
-                cls_rows.to(torch.int32).contiguous(),
-                pi_hat.contiguous(), pbest_before.contiguous(),
-                mixture0.contiguous())                      # (K,)
-        else:
-            grp = (ps.grp_off if ps.grp_off is not None
-                   else torch.empty(0, dtype=torch.int32,
-                                    device=A16.device))
-            h_after = O._ext.pair_gemm_entropy(
-                A16, tables.egw, ps.vmask, ps.pair_c,
-                pi_hat.contiguous(), pbest_before.contiguous(),
-                mixture0.contiguous(), ps.tile, 0, grp)     # (K,)
+        if h_after is None:
+            h_after = _h_after_kernels(tables, ps, cls_rows, pbest_before,
+                                       pi_hat, mixture0)
         h_base = h_after.index_select(0, ps.base_pos).contiguous()
         q = O._ext.pair_eig_finalize(
             h_after, h_base, ps.pair_c,
@@ -393,8 +563,9 @@ def eig_pairs(tables, ps: PairStructure, cls_rows: torch.Tensor,
             adjusted.contiguous(), row_sums.contiguous(),
             float(H_before))                                # (B,)
         return q
-    h_after = pair_h_after(tables, ps, cls_rows, pbest_before,
-                           pi_hat, mixture0)
+    if h_after is None:
+        h_after = pair_h_after(tables, ps, cls_rows, pbest_before,
+                               pi_hat, mixture0)
     eig_n = eig_from_pairs(h_after, ps, adjusted, row_sums, H_before)
     return eig_n[ps.cand_ids]
 

@@ -31,7 +31,7 @@ from ..base import ModelSelector
 from ..parallel import Comm, get_comm
 from .. import ops
 from ..ops import sharded as shops
-from ..util import DEBUG, _check, mirror_fits
+from ..util import DEBUG, _check, mirror_fits, pair_cache_fits
 
 import os
 DEBUG_VIZ = os.environ.get("CODA_AMD_DEBUG_VIZ") == "1"
@@ -71,6 +71,15 @@ class CODA(ModelSelector):
         self._pair_row_of = None     # point id -> row in the static set
         self._active_mask = None     # (B_full,) bool device mask
         self._tables_dirty = set()   # class rows touched since last build
+        # pair cache (ops/pair.py PairCache) over the STATIC structure:
+        # the per-pair state a label on another class leaves unchanged.
+        # A label then re-evaluates one class's pairs, not all K.
+        # CODA_AMD_NO_PAIR_CACHE=1 forces the uncached kernels.
+        self._pair_cache = None
+        self._pair_cache_stale = set()   # classes whose table rows moved
+        self._pair_cache_declined = False  # gate/fit said no for this set
+        self._use_pair_cache = \
+            os.environ.get("CODA_AMD_NO_PAIR_CACHE") != "1"
         self._posterior_version = 0  # bumped by add_label
         self._pbest_rows_cache = (-1, None)
         # hipGraph capture of the post-label update pipeline (Dirichlet row
@@ -323,14 +332,72 @@ class CODA(ModelSelector):
         if self._tables is None:
             self._tables = tops.table_precompute(
                 alpha_cc, beta_cc, num_points=self.num_points)
+            self._drop_pair_cache()
         elif self._tables_dirty:
             tops.table_update_rows(self._tables, alpha_cc, beta_cc,
                                    sorted(self._tables_dirty))
+            if self._pair_cache is not None:
+                # whichever path refreshed the rows, the cache owes
+                # these classes a refresh before its next read
+                self._pair_cache_stale |= self._tables_dirty
         self._tables_dirty.clear()
         if want_egw and self._tables.egw is None:
             from ..ops import pair as pops
             self._tables = pops.attach_pair_tables(self._tables)
         return self._tables
+
+    # -- pair cache ----------------------------------------------------
+    def _drop_pair_cache(self):
+        """The one place the cache (and its scratch) is invalidated:
+        called by whatever replaces _tables or _pairs_static."""
+        self._pair_cache = None
+        self._pair_cache_stale = set()
+        self._pair_cache_declined = False
+
+    def _pair_cache_wanted(self) -> bool:
+        """The scope gate, as one predicate: the static full-pool
+        structure on the fused B-resident route, a cache that fits with
+        headroom, and no CODA_AMD_NO_PAIR_CACHE."""
+        from ..ops import pair as pops
+        if (not self._use_pair_cache or self._pairs_static is None
+                or self._tables is None):
+            return False
+        ps, _ = self._pairs_static
+        return (pops.pair_cache_gate(self._tables, ps)
+                and pair_cache_fits(
+                    self.device, pops.pair_cache_bytes(ps, self.H)))
+
+    def _sync_pair_cache(self):
+        """Build the cache where the static structure and the pair
+        tables first both exist (never under capture), or bring it up to
+        date: one one-class refresh per class whose table rows moved
+        since its last read. Returns the cache or None (uncached path)."""
+        from ..ops import pair as pops
+        if self._pair_cache is None:
+            if self._pair_cache_declined:
+                return None
+            if not self._pair_cache_wanted():
+                self._pair_cache_declined = True
+                return None
+            ps, cls_rows = self._pairs_static
+            self._pair_cache = pops.pair_cache_build(self._tables, ps,
+                                                     cls_rows)
+            self._pair_cache_stale = set()
+            # a graph captured without the cache neither refreshes nor
+            # reads it: recapture
+            self._label_graph = None
+            self._acq_graph = None
+            self._acq_fresh = False
+            return self._pair_cache
+        if self._pair_cache_stale:
+            ps, cls_rows = self._pairs_static
+            for y in sorted(self._pair_cache_stale):
+                y_arg = y if self._pair_cache.pbn is not None else \
+                    torch.tensor([y], dtype=torch.long, device=self.device)
+                pops.pair_cache_refresh(self._pair_cache, self._tables,
+                                        ps, cls_rows, y_arg)
+            self._pair_cache_stale = set()
+        return self._pair_cache
 
     def _eig_pair(self, candidate_ids):
         """v3 hit-sparse EIG over the candidate set (ops/pair.py).
@@ -363,6 +430,7 @@ class CODA(ModelSelector):
             if self._pairs_static is None:
                 ids = torch.tensor(list(candidate_ids), device=self.device)
                 self._pairs_static = build(ids)
+                self._drop_pair_cache()
                 self._pair_row_of = {int(p): i
                                      for i, p in enumerate(ids.tolist())}
                 self._active_mask = torch.ones(
@@ -375,9 +443,16 @@ class CODA(ModelSelector):
             ps, cls_rows = build(cand)
             mask, perm = None, self._interleave_perm(cand.numel())
         if ps.cand_ids.numel():
+            h_after = None
+            if mask is not None:   # the static structure: cached route
+                cache = self._sync_pair_cache()
+                if cache is not None:
+                    h_after = pops.pair_cache_h_after(
+                        cache, ps, self.pi_hat, pbest_before, mixture0)
             q = pops.eig_pairs(tables, ps, cls_rows, pbest_before,
                                self.pi_hat, mixture0, H_before,
-                               self._adjusted, self._row_sums)
+                               self._adjusted, self._row_sums,
+                               h_after=h_after)
         else:  # more ranks than candidates
             q = torch.empty(0, device=self.device)
         if self._replicated:
@@ -508,13 +583,21 @@ class CODA(ModelSelector):
         ps, _ = self._pairs_static
         rows, pi = self._g_rows, self._g_pi
         mixture0, H0 = ops.mixture_entropy(rows, pi)
-        A16 = ops._ext.pair_dsum_es(t.delta16, t.dall, ps.pair_c,
-                                    ps.pair_neg, ps.seg_off, ps.seg_h)
-        grp = (ps.grp_off if ps.grp_off is not None
-               else torch.empty(0, dtype=torch.int32, device=A16.device))
-        h_after = ops._ext.pair_gemm_entropy(
-            A16, t.egw, ps.vmask, ps.pair_c, pi, rows,
-            mixture0.contiguous(), ps.tile, 0, grp)
+        if self._pair_cache is not None:
+            # one streaming pass over the cache (kept current by
+            # _label_update_body's one-class refresh)
+            from ..ops import pair as pops
+            h_after = pops.pair_cache_h_after(self._pair_cache, ps, pi,
+                                              rows, mixture0)
+        else:
+            A16 = ops._ext.pair_dsum_es(t.delta16, t.dall, ps.pair_c,
+                                        ps.pair_neg, ps.seg_off, ps.seg_h)
+            grp = (ps.grp_off if ps.grp_off is not None
+                   else torch.empty(0, dtype=torch.int32,
+                                    device=A16.device))
+            h_after = ops._ext.pair_gemm_entropy(
+                A16, t.egw, ps.vmask, ps.pair_c, pi, rows,
+                mixture0.contiguous(), ps.tile, 0, grp)
         # H_before enters as an in-graph tensor op (the kernel's scalar
         # argument would be frozen at capture value)
         h_base = h_after.index_select(0, ps.base_pos).contiguous()
@@ -597,6 +680,7 @@ class CODA(ModelSelector):
     def _graphed_acquire(self):
         if self._acq_graph is None:
             self._init_acq_buffers()
+            self._sync_pair_cache()    # outside the capture
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
@@ -740,6 +824,14 @@ class CODA(ModelSelector):
                     t.delta16.index_copy_(
                         0, y_t, t.delta.index_select(0, y_t)
                         .to(torch.float16))
+            if self._pair_cache is not None:
+                # class y's table rows just moved: re-evaluate its run
+                # of pairs (commit -> refresh -> entropy pass, in stream
+                # order; y is read on the device, so this captures)
+                from ..ops import pair as pops
+                ps, cls_rows = self._pairs_static
+                pops.pair_cache_refresh(self._pair_cache, t, ps, cls_rows,
+                                        y_t)
         # posterior rows: add_label moves only Dirichlet row y, so only
         # class y's Beta column - hence only pbest row y - changes.
         # _g_rows was seeded with the full (C, Hl) rows at graph init;
@@ -752,6 +844,8 @@ class CODA(ModelSelector):
 
     def _graphed_add_label(self, idx: int, true_class: int):
         if self._label_graph is None:
+            self._sync_pair_cache()    # outside the capture
+            self._acq_graph = None     # captured on the buffers below
             self._g_idx = torch.zeros(1, dtype=torch.long,
                                       device=self.device)
             self._g_y = torch.zeros(1, dtype=torch.long, device=self.device)

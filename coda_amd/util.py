@@ -49,6 +49,16 @@ def mirror_fits(device, pool_bytes: int, pool_resident: bool = True) -> bool:
     return free > need + MIRROR_SPARE_BYTES
 
 
+def pair_cache_fits(device, cache_bytes: int) -> bool:
+    """Same headroom rule for the pair cache (K*H*4 bytes plus its
+    one-off build operand): allocate only when 24 GB stay free with it
+    resident. Host memory is not rationed."""
+    if torch.device(device).type != "cuda":
+        return True
+    free, _ = torch.cuda.mem_get_info(device)
+    return free > cache_bytes + MIRROR_SPARE_BYTES
+
+
 class Ensemble:
     """Mean-ensemble consensus over the model axis (reference
     coda/util.py:7-14)."""
