@@ -4,7 +4,8 @@ The reference's unit of resume is a whole seed run (SURVEY.md section 5.4:
 all durable state lives in the tracking DB). At large scales a single run
 is expensive, so selectors can be checkpointed mid-run: a selector's full
 state is small and explicit (for CODA: dirichlets (H,C,C), the
-labeled/unlabeled bookkeeping, step counter - coda/coda.py:196-203).
+labeled/unlabeled bookkeeping, step counter - coda/coda.py:196-203 -
+plus the (N,C) pi_hat accumulators this engine maintains incrementally).
 
 Covers every built-in selector via a field registry; sharded CODA
 checkpoints its LOCAL Dirichlet shard (each rank writes
@@ -19,8 +20,12 @@ import torch
 
 # selector attribute names that form the restorable state, per class name
 _STATE_FIELDS = {
+    # _adjusted/_row_sums: the (N, C) pi_hat accumulators, i.e. the full
+    # contraction at init plus every label's rank-1 increment. Recomputing
+    # them from the Dirichlets moves their last bits, and the restored
+    # run's q values with them.
     "CODA": ["dirichlets", "labeled_idxs", "labels", "unlabeled_idxs",
-             "q_vals", "stochastic", "step"],
+             "q_vals", "stochastic", "step", "_adjusted", "_row_sums"],
     "IID": ["d_l_idxs", "d_l_ys", "d_u_idxs", "_loss_sum", "stochastic"],
     "Uncertainty": ["d_l_idxs", "d_l_ys", "d_u_idxs", "_loss_sum",
                     "stochastic"],
@@ -57,7 +62,12 @@ def load_state_dict(selector, state: Dict[str, Any]):
         raise ValueError(f"Checkpoint is for {state.get('__class__')}, "
                          f"selector is {cls}")
     device = getattr(selector, "device", "cpu")
+    # checkpoints written before CODA saved its pi_hat accumulators
+    # restore through the full contraction
+    carried = cls != "CODA" or "_adjusted" in state
     for f in _STATE_FIELDS[cls]:
+        if not carried and f in ("_adjusted", "_row_sums"):
+            continue
         v = state[f]
         cur = getattr(selector, f, None)
         if torch.is_tensor(cur):
@@ -72,35 +82,8 @@ def load_state_dict(selector, state: Dict[str, Any]):
         selector._rebuild_unlabeled_mask()   # mirrors d_u_idxs on device
     # derived state that depends on the posterior
     if cls == "CODA":
-        selector._tables = None       # force a fresh v2 table build
-        selector._tables_dirty = set()
-        selector._posterior_version += 1
-        selector._pbest_rows_cache = (-1, None)
-        selector._label_graph = None  # graph buffers alias replaced state
-        selector._acq_graph = None
-        selector._acq_out = None      # sized for the stale pair set
-        selector._acq_fresh = False
-        selector._acq_saved = None
-        selector._merged_acq = False
-        selector._drop_pair_cache()    # built from the replaced tables
-        selector._pairs_static = None  # hit structure covers a stale set
-        selector._pair_row_of = None
-        selector._active_mask = None
-        from sortedcontainers import SortedList
-        selector._active_candidates = SortedList(
-            i for i in selector.unlabeled_idxs
-            if selector._disagreement_host[i])
-        if getattr(selector, "_replicated", False):
-            from coda_amd import ops
-            a_l, b_l = ops.dirichlet_to_beta(selector.dirichlets)
-            sizes = selector.comm.shard_sizes(selector.H)
-            order = selector.comm.unshard_order(selector.H) \
-                .to(selector.device)
-            selector._alpha_g = selector.comm.all_gather_cat(
-                a_l, dim=0, sizes=sizes)[order].contiguous()
-            selector._beta_g = selector.comm.all_gather_cat(
-                b_l, dim=0, sizes=sizes)[order].contiguous()
-        selector.update_pi_hat()
+        selector.reset_derived_state()
+        selector.update_pi_hat(recontract=not carried)
     return selector
 
 

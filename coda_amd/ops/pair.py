@@ -546,7 +546,13 @@ def eig_pairs(tables, ps: PairStructure, cls_rows: torch.Tensor,
     Dispatches the per-pair work to the HIP kernels when available
     (GPU), else the eager formulation. h_after: the (K,) per-pair
     entropies when the caller already has them (pair_cache_h_after).
+    H_before=None leaves that term out (the result is EIG - H_before):
+    under graph capture it is a device scalar, which as a kernel
+    argument would need a host read and freeze at its capture value, so
+    the captured caller adds it in-stream.
     """
+    if H_before is None:
+        H_before = 0.0
     import coda_amd.ops as O
     EG = tables.EG
     C, H, _, P = EG.shape
@@ -579,7 +585,10 @@ def attach_pair_tables(tables):
     delta16 (C, H, P) fp16 — the dsum kernel's table (halves its
     traffic; |delta| < 116 fits fp16 range, and the 5e-4 relative
     rounding is below the bf16 rounding of the A operand it feeds).
+    Tables that carry them already come back as they are.
     """
+    if tables.egw is not None:
+        return tables
     EG, s_base, w = tables.EG, tables.s_base, tables.weights
     C, H, _, P = EG.shape
     esb = torch.exp2(s_base) * w                            # (C, P)

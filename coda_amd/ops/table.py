@@ -279,6 +279,48 @@ def table_update_rows(tables: EigTables, alpha_cc: torch.Tensor,
     return tables
 
 
+def table_commit_row(tables: EigTables, dirichlets: torch.Tensor,
+                     y_t: torch.Tensor):
+    """table_update_rows for ONE class given as a (1,) int64 DEVICE
+    tensor: reads Dirichlet row y on the device and writes that class's
+    slice of every table in stream order - static shapes, no host sync,
+    so it records into a hipGraph. Returns the class's (H,) Beta columns
+    (a_col, b_col) as the kernels computed them."""
+    import coda_amd.ops as O
+    t = tables
+    H = dirichlets.shape[0]
+    if (t.eg16 is not None and t.egw is not None
+            and t.delta16 is not None and t.dall is not None
+            and O.hip_available()):
+        # one fused commit (trc_* kernels in pbest.hip): the torch chain
+        # below was ~14 in-graph launches incl. two 32-thread strided
+        # reductions (10-24 us each)
+        return O._ext.table_commit_row(
+            dirichlets, y_t, t.EG, t.delta, t.s_base, t.weights, t.eg16,
+            t.egw, t.delta16, t.dall, 1.0)
+    row = dirichlets.index_select(1, y_t).squeeze(1)            # (H, C)
+    a_col = row.gather(1, y_t.view(1, 1).expand(H, 1)) \
+        .squeeze(1).contiguous()
+    b_col = (row.sum(1) - a_col).contiguous()
+    eg, lc = O._ext.beta_row_tables(a_col, b_col, 1.0)
+    t.EG.index_copy_(0, y_t, eg.unsqueeze(0))
+    if t.eg16 is not None:
+        t.eg16.index_copy_(
+            0, y_t, eg.reshape(1, 2 * H, -1).to(torch.bfloat16))
+    t.delta.index_copy_(0, y_t, (lc[:, 1] - lc[:, 0]).unsqueeze(0))
+    t.s_base.index_copy_(0, y_t, lc[:, 0].sum(0).unsqueeze(0))
+    if t.dall is not None:
+        t.dall.index_copy_(0, y_t, t.delta.index_select(0, y_t).sum(1))
+    if t.egw is not None:
+        esb = torch.exp2(t.s_base.index_select(0, y_t)) * t.weights  # (1, P)
+        t.egw.index_copy_(
+            0, y_t, (eg.reshape(1, 2 * H, -1)
+                     * esb.unsqueeze(1)).to(torch.bfloat16))
+        t.delta16.index_copy_(
+            0, y_t, t.delta.index_select(0, y_t).to(torch.float16))
+    return a_col, b_col
+
+
 # ---------------------------------------------------------------------------
 # Sharded v2: the model axis is split across ranks; each rank holds table
 # slices for its local models. The cross-rank coupling is carried by an

@@ -22,7 +22,6 @@ the math):
 from __future__ import annotations
 
 import random
-import struct
 
 import torch
 from sortedcontainers import SortedList
@@ -30,11 +29,40 @@ from sortedcontainers import SortedList
 from ..base import ModelSelector
 from ..parallel import Comm, get_comm
 from .. import ops
+from ..ops import pair as pops
 from ..ops import sharded as shops
-from ..util import DEBUG, _check, mirror_fits, pair_cache_fits
+from ..ops import table as tops
+from ..util import DEBUG, _check, mirror_fits
+from .pair_acq import PairAcquisition, tied_choice
 
 import os
 DEBUG_VIZ = os.environ.get("CODA_AMD_DEBUG_VIZ") == "1"
+
+# self._acq_pending when the next acquisition's result waits in the
+# device result buffers (a host result waits as its (index, q) tuple)
+_ON_DEVICE = object()
+
+
+def _warm_and_capture(body, read=None):
+    """Capture body() into a hipGraph; returns (graph, read()).
+
+    The warm-up executes the body for real on a side stream, as stream
+    capture requires; the capture pass then only RECORDS the ops (no
+    execution, no state change), so whatever the body computes has
+    happened exactly once when this returns and the caller must not
+    additionally replay. read() runs between the two, on the warm-up's
+    results, before the capture rebinds the body's output tensors."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        body()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    first = read() if read is not None else None
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        body()
+    return g, first
 
 
 class CODA(ModelSelector):
@@ -66,32 +94,14 @@ class CODA(ModelSelector):
         # (ops/pair.py - the full-pool no-prefilter fast path). 'auto'
         # resolves per device at eig time.
         self.eig_impl = eig_impl
-        self._tables = None          # persistent v2 curve tables
-        self._pairs_static = None    # v3 static hit structure (full pool)
-        self._pair_row_of = None     # point id -> row in the static set
-        self._active_mask = None     # (B_full,) bool device mask
-        self._tables_dirty = set()   # class rows touched since last build
-        # pair cache (ops/pair.py PairCache) over the STATIC structure:
-        # the per-pair state a label on another class leaves unchanged.
-        # A label then re-evaluates one class's pairs, not all K.
-        # CODA_AMD_NO_PAIR_CACHE=1 forces the uncached kernels.
-        self._pair_cache = None
-        self._pair_cache_stale = set()   # classes whose table rows moved
-        self._pair_cache_declined = False  # gate/fit said no for this set
+        # CODA_AMD_NO_PAIR_CACHE=1 forces the uncached pair kernels
         self._use_pair_cache = \
             os.environ.get("CODA_AMD_NO_PAIR_CACHE") != "1"
-        self._posterior_version = 0  # bumped by add_label
-        self._pbest_rows_cache = (-1, None)
+        self._est_distinct = None    # _hit_sparse's one-off estimate
         # hipGraph capture of the post-label update pipeline (Dirichlet row
         # update -> rank-1 pi_hat -> table row refresh -> posterior rows):
         # ~20 static-shape launches replayed as one graph. Auto on
         # single-device GPU; CODA_AMD_NO_GRAPH=1 disables.
-        self._label_graph = None
-        # hipGraph of the full-pool pair acquisition (static hit
-        # structure + static table/posterior buffers -> the whole
-        # get_next tensor pipeline incl. argmax/tie counting replays as
-        # one graph; one host sync per step)
-        self._acq_graph = None
         # (debug guards synchronize per op and cannot run under stream
         # capture - graph replay is a production-mode path)
         self._use_label_graph = (
@@ -132,7 +142,6 @@ class CODA(ModelSelector):
             self.comm.is_distributed and self.H <= 1024
             and self.C <= 32767 and eig_impl in ("auto", "pair"))
         self.classes_global = None
-        self._alpha_g = self._beta_g = None
         if self._replicated:
             # gather in int32 (gloo has no int16 collectives), store
             # int16 - at the 8-GPU 1024x1M config that's 2 GB resident
@@ -177,17 +186,6 @@ class CODA(ModelSelector):
         soft_conf = ops.confusion_prior(pseudo, preds)    # (Hl, C, C)
         self.dirichlets = ops.init_dirichlets(
             soft_conf, self.prior_strength, disable_diag_prior, multiplier)
-        if self._replicated:
-            # replicated global diagonal-Beta view (gathered once; kept
-            # current locally from classes_global on every label)
-            a_l, b_l = ops.dirichlet_to_beta(self.dirichlets)  # (Hl, C)
-            sizes = self.comm.shard_sizes(self.H)
-            order = self.comm.unshard_order(self.H).to(self.device)
-            self._alpha_g = self.comm.all_gather_cat(
-                a_l, dim=0, sizes=sizes)[order].contiguous()
-            self._beta_g = self.comm.all_gather_cat(
-                b_l, dim=0, sizes=sizes)[order].contiguous()
-        self.update_pi_hat()
 
         # static disagreement mask (K12): "not all models agree".
         if self._replicated:
@@ -207,18 +205,63 @@ class CODA(ModelSelector):
         # host-side copy for the per-step candidate filter (indexing a GPU
         # tensor point-by-point would be one device sync per point)
         self._disagreement_host = self._disagreement.cpu().tolist()
-        # persistently maintained unlabeled-and-disagreeing candidates
-        # (the mask is static; add_label removes one entry). SortedList
-        # keeps the reference's ascending order with O(log N) removal -
-        # a plain list.remove is an O(N) scan per label.
-        self._active_candidates = SortedList(
-            i for i in range(self.N) if self._disagreement_host[i])
 
         self.labeled_idxs, self.labels = [], []
         self.unlabeled_idxs = SortedList(range(self.N))
         self.q_vals = []
         self.stochastic = False
         self.step = 0
+        self.reset_derived_state()
+        self.update_pi_hat()
+
+    def reset_derived_state(self):
+        """Put everything derived from the restorable state (the
+        Dirichlets and the labeled/unlabeled bookkeeping) back to what a
+        fresh selector holds. Called by __init__ and, followed by
+        update_pi_hat(), by whatever replaces that state (checkpoint
+        restore): a new derived field is added here and nowhere else."""
+        self._tables = None          # persistent v2 curve tables
+        self._tables_dirty = set()   # class rows touched since last build
+        # full-pool pair acquisition over the static candidate set: hit
+        # structure, active mask, pair cache, result buffers
+        self._pair_acq = None
+        self._posterior_version = 0  # bumped by add_label
+        self._pbest_rows_cache = (-1, None)
+        # _label_graph: the post-label update pipeline (see
+        # _use_label_graph). _acq_graph: the full-pool pair acquisition
+        # (static hit structure + static table/posterior buffers -> the
+        # whole get_next tensor pipeline incl. argmax/tie counting
+        # replays as one graph; one host sync per step)
+        self._drop_graphs()
+        self._merged_acq = False     # _label_graph also acquires
+        # the label graph's static inputs (1,) int64 and outputs
+        self._g_idx = self._g_y = self._g_pi = self._g_rows = None
+        self._alpha_g, self._beta_g = self._gather_global_betas()
+        # persistently maintained unlabeled-and-disagreeing candidates
+        # (the mask is static; add_label removes one entry). SortedList
+        # keeps the reference's ascending order with O(log N) removal -
+        # a plain list.remove is an O(N) scan per label.
+        self._active_candidates = SortedList(
+            i for i in self.unlabeled_idxs if self._disagreement_host[i])
+
+    def _drop_graphs(self):
+        """Captured graphs alias the buffers they were captured on, and
+        a pending acquisition result was computed by one of them: all
+        three go together."""
+        self._label_graph = None
+        self._acq_graph = None
+        self._acq_pending = None
+
+    def _gather_global_betas(self):
+        """Replicated global (H, C) diagonal-Beta view (gathered here;
+        kept current locally from classes_global on every label)."""
+        if not self._replicated:
+            return None, None
+        a_l, b_l = ops.dirichlet_to_beta(self.dirichlets)  # (Hl, C)
+        sizes = self.comm.shard_sizes(self.H)
+        order = self.comm.unshard_order(self.H).to(self.device)
+        return tuple(self.comm.all_gather_cat(
+            t, dim=0, sizes=sizes)[order].contiguous() for t in (a_l, b_l))
 
     @classmethod
     def from_args(cls, dataset, args, comm=None):
@@ -248,14 +291,23 @@ class CODA(ModelSelector):
             self.stochastic = True
         return idxs
 
-    def update_pi_hat(self):
+    def update_pi_hat(self, recontract: bool = True):
         """Confusion-adjusted class marginals (K5; all-reduce over H).
 
         Runs the FULL contraction (one packed bf16 MFMA GEMM on GPU).
-        Called once at init and by checkpoint restore; per-label updates
-        go through the exact rank-1 incremental path in add_label
-        (ops.pi_hat_delta), which is O(H*N) instead of O(H*N*C^2).
+        Called once at init; per-label updates go through the exact
+        rank-1 incremental path in add_label (ops.pi_hat_delta), which
+        is O(H*N) instead of O(H*N*C^2). recontract=False keeps the
+        maintained adjusted/row_sums and only re-derives pi_hat from
+        them: a checkpoint carries the two, because the contraction
+        does not reproduce the sum of the increments to the last bit
+        (nor, on the bf16 route, to fp32 precision) and a restored run
+        has to continue the run it was saved from.
         """
+        if not recontract:
+            self.pi_hat = self._pi_marginal()
+            self._pi_xi_cache = None
+            return
         if self.pi_hat_precision == "bf16":
             # N-chunked pack + bf16 MFMA GEMM: never holds the full
             # (N, H*C) operand, so million-point pools fit alongside the
@@ -267,9 +319,10 @@ class CODA(ModelSelector):
         self.comm.all_reduce_(adjusted)
         self._adjusted = adjusted
         self._row_sums = adjusted.sum(dim=-1)
-        self._refresh_pi_hat()
+        self.pi_hat = self._pi_marginal()
+        self._pi_xi_cache = None
 
-    def _refresh_pi_hat(self):
+    def _pi_marginal(self):
         """pi_hat (C,) from the maintained adjusted/row_sums WITHOUT
         materializing the (N, C) per-item normalization: the marginal is
         one GEMV, pi = adjusted^T @ (1/rowsum), then self-normalized
@@ -284,8 +337,7 @@ class CODA(ModelSelector):
             # row-vector @ matrix streams adjusted once; transposed mv is
             # 5x slower on ROCm (strided column reduction)
             pi = inv @ self._adjusted
-        self.pi_hat = pi / pi.sum()
-        self._pi_xi_cache = None
+        return pi / pi.sum()
 
     @property
     def pi_hat_xi(self):
@@ -328,76 +380,37 @@ class CODA(ModelSelector):
 
     def _refresh_tables(self, alpha_cc, beta_cc, want_egw: bool):
         """Build or incrementally refresh the per-step curve tables."""
-        from ..ops import table as tops
+        acq = self._pair_acq
         if self._tables is None:
             self._tables = tops.table_precompute(
                 alpha_cc, beta_cc, num_points=self.num_points)
-            self._drop_pair_cache()
+            if acq is not None:
+                acq.drop_cache()
         elif self._tables_dirty:
             tops.table_update_rows(self._tables, alpha_cc, beta_cc,
                                    sorted(self._tables_dirty))
-            if self._pair_cache is not None:
+            if acq is not None and acq.cache is not None:
                 # whichever path refreshed the rows, the cache owes
                 # these classes a refresh before its next read
-                self._pair_cache_stale |= self._tables_dirty
+                acq.stale |= self._tables_dirty
         self._tables_dirty.clear()
-        if want_egw and self._tables.egw is None:
-            from ..ops import pair as pops
+        if want_egw:
             self._tables = pops.attach_pair_tables(self._tables)
         return self._tables
 
-    # -- pair cache ----------------------------------------------------
-    def _drop_pair_cache(self):
-        """The one place the cache (and its scratch) is invalidated:
-        called by whatever replaces _tables or _pairs_static."""
-        self._pair_cache = None
-        self._pair_cache_stale = set()
-        self._pair_cache_declined = False
-
-    def _pair_cache_wanted(self) -> bool:
-        """The scope gate, as one predicate: the static full-pool
-        structure on the fused B-resident route, a cache that fits with
-        headroom, and no CODA_AMD_NO_PAIR_CACHE."""
-        from ..ops import pair as pops
-        if (not self._use_pair_cache or self._pairs_static is None
-                or self._tables is None):
-            return False
-        ps, _ = self._pairs_static
-        return (pops.pair_cache_gate(self._tables, ps)
-                and pair_cache_fits(
-                    self.device, pops.pair_cache_bytes(ps, self.H)))
-
     def _sync_pair_cache(self):
-        """Build the cache where the static structure and the pair
-        tables first both exist (never under capture), or bring it up to
-        date: one one-class refresh per class whose table rows moved
-        since its last read. Returns the cache or None (uncached path)."""
-        from ..ops import pair as pops
-        if self._pair_cache is None:
-            if self._pair_cache_declined:
-                return None
-            if not self._pair_cache_wanted():
-                self._pair_cache_declined = True
-                return None
-            ps, cls_rows = self._pairs_static
-            self._pair_cache = pops.pair_cache_build(self._tables, ps,
-                                                     cls_rows)
-            self._pair_cache_stale = set()
+        """The pair cache brought up to date with the tables (built on
+        first use), or None on the uncached path. Never under capture."""
+        acq = self._pair_acq
+        if acq is None:
+            return None
+        had = acq.cache is not None
+        cache = acq.sync_cache(self._tables)
+        if cache is not None and not had:
             # a graph captured without the cache neither refreshes nor
             # reads it: recapture
-            self._label_graph = None
-            self._acq_graph = None
-            self._acq_fresh = False
-            return self._pair_cache
-        if self._pair_cache_stale:
-            ps, cls_rows = self._pairs_static
-            for y in sorted(self._pair_cache_stale):
-                y_arg = y if self._pair_cache.pbn is not None else \
-                    torch.tensor([y], dtype=torch.long, device=self.device)
-                pops.pair_cache_refresh(self._pair_cache, self._tables,
-                                        ps, cls_rows, y_arg)
-            self._pair_cache_stale = set()
-        return self._pair_cache
+            self._drop_graphs()
+        return cache
 
     def _eig_pair(self, candidate_ids):
         """v3 hit-sparse EIG over the candidate set (ops/pair.py).
@@ -408,7 +421,6 @@ class CODA(ModelSelector):
         values are all-gathered and re-interleaved - O(B) bytes per
         step on the wire.
         """
-        from ..ops import pair as pops
         alpha_cc, beta_cc = self._beta_view()
         tables = self._refresh_tables(alpha_cc, beta_cc, want_egw=True)
         pbest_before = self._pbest_rows_before()            # (C, H)
@@ -427,17 +439,14 @@ class CODA(ModelSelector):
         if candidate_ids is self._active_candidates:
             # full-pool acquisition: the hit structure is static (argmax
             # classes never change); labeled points are masked at gather
-            if self._pairs_static is None:
+            if self._pair_acq is None:
                 ids = torch.tensor(list(candidate_ids), device=self.device)
-                self._pairs_static = build(ids)
-                self._drop_pair_cache()
-                self._pair_row_of = {int(p): i
-                                     for i, p in enumerate(ids.tolist())}
-                self._active_mask = torch.ones(
-                    ids.numel(), dtype=torch.bool, device=self.device)
-                self._shard_perm = self._interleave_perm(ids.numel())
-            ps, cls_rows = self._pairs_static
-            mask, perm = self._active_mask, self._shard_perm
+                self._pair_acq = PairAcquisition(
+                    *build(ids), ids, self._interleave_perm(ids.numel()),
+                    self._use_pair_cache)
+            acq = self._pair_acq
+            ps, cls_rows, mask, perm = (acq.ps, acq.cls_rows, acq.active,
+                                        acq.perm)
         else:
             cand = torch.tensor(list(candidate_ids), device=self.device)
             ps, cls_rows = build(cand)
@@ -479,7 +488,7 @@ class CODA(ModelSelector):
     def _hit_sparse(self) -> bool:
         """True when candidates hit few distinct classes (the pair
         engine's regime): estimated from a 1024-point sample once."""
-        if not hasattr(self, "_est_distinct"):
+        if self._est_distinct is None:
             src = self.classes_global if self._replicated else self.classes
             n = src.shape[1]
             g = torch.Generator(device="cpu").manual_seed(0)
@@ -537,7 +546,6 @@ class CODA(ModelSelector):
             impl = "table" if self.device.type == "cuda" else "fused"
         tables = s_base_all = None
         if impl == "table":
-            from ..ops import table as tops
             tables = self._refresh_tables(alpha_cc, beta_cc,
                                           want_egw=False)
             if self.comm.is_distributed:
@@ -549,7 +557,6 @@ class CODA(ModelSelector):
             chunk_classes = self.classes[:, ids].t().contiguous()  # (B, Hl)
             pi_xi = self._pi_xi_rows(ids)                          # (B, C)
             if self.comm.is_distributed and tables is not None:
-                from ..ops import table as tops
                 eig = tops.eig_chunk_table_sharded(
                     tables, s_base_all, chunk_classes, pbest_before,
                     self.pi_hat, pi_xi, mixture0, H_before, self.comm,
@@ -560,7 +567,6 @@ class CODA(ModelSelector):
                     self.pi_hat, pi_xi, mixture0, H_before, self.comm,
                     num_points=self.num_points)
             elif tables is not None:
-                from ..ops import table as tops
                 eig = tops.eig_chunk_table(
                     tables, chunk_classes, pbest_before, self.pi_hat,
                     pi_xi, mixture0, H_before)
@@ -579,99 +585,35 @@ class CODA(ModelSelector):
         mixture entropy from the label-graph's posterior rows/pi_hat,
         the three pair kernels, labeled-candidate masking, argmax and
         tie counting. Captured once; identical math to _eig_pair."""
-        t = self._tables
-        ps, _ = self._pairs_static
+        acq = self._pair_acq
         rows, pi = self._g_rows, self._g_pi
         mixture0, H0 = ops.mixture_entropy(rows, pi)
-        if self._pair_cache is not None:
-            # one streaming pass over the cache (kept current by
-            # _label_update_body's one-class refresh)
-            from ..ops import pair as pops
-            h_after = pops.pair_cache_h_after(self._pair_cache, ps, pi,
-                                              rows, mixture0)
-        else:
-            A16 = ops._ext.pair_dsum_es(t.delta16, t.dall, ps.pair_c,
-                                        ps.pair_neg, ps.seg_off, ps.seg_h)
-            grp = (ps.grp_off if ps.grp_off is not None
-                   else torch.empty(0, dtype=torch.int32,
-                                    device=A16.device))
-            h_after = ops._ext.pair_gemm_entropy(
-                A16, t.egw, ps.vmask, ps.pair_c, pi, rows,
-                mixture0.contiguous(), ps.tile, 0, grp)
+        # cached: one streaming pass over the cache (kept current by
+        # _graph_label_update's one-class refresh)
+        h_after = None if acq.cache is None else pops.pair_cache_h_after(
+            acq.cache, acq.ps, pi, rows, mixture0)
         # H_before enters as an in-graph tensor op (the kernel's scalar
         # argument would be frozen at capture value)
-        h_base = h_after.index_select(0, ps.base_pos).contiguous()
-        q0 = ops._ext.pair_eig_finalize(
-            h_after, h_base, ps.pair_c, ps.cand_off,
-            ps.cand_ck, ps.cand_ids, self._adjusted, self._row_sums,
-            0.0)
-        # fused epilogue: qbuf = active ? H0 + q0 : -inf; _acq_out =
+        q0 = pops.eig_pairs(self._tables, acq.ps, acq.cls_rows, rows, pi,
+                            mixture0, None, self._adjusted, self._row_sums,
+                            h_after=h_after)
+        # fused epilogue: qbuf = active ? H0 + q0 : -inf; out =
         # [masked max, first argmax, isclose tie count].  Replaces the
         # ~10-launch torch chain (where/max/isclose/sum/copies,
         # ~120 us/step at B=50k); identical semantics - when the tie
         # count is 1 the argmax is unique, and ties go through the
         # seeded host random.choice either way (_acq_result).
         ops._ext.acq_select(q0.contiguous(), H0.reshape(1).contiguous(),
-                            self._active_mask, self._acq_qbuf,
-                            self._acq_out, self._acq_ties)
+                            acq.active, acq.qbuf, acq.out, acq.ties)
 
     def _acq_result(self):
-        self._acq_out_host.copy_(self._acq_out)
-        bv, bi, nt = self._acq_out_host.tolist()
-        bi, nt = int(bi), int(nt)
-        if bi < 0:
-            raise RuntimeError("acquisition ran with no active "
-                               "candidates (pool exhausted?)")
-        if nt > 1:
-            # same tie semantics as the eager path: active candidates
-            # ascend by point id in both orderings.  The fused epilogue
-            # collected (position, q value) pairs already (unordered
-            # slots); sorting restores the ascending order the seeded
-            # random.choice tie-break expects.
-            if nt < self._acq_ties.numel():
-                th = self._acq_ties_host[:1 + nt]
-                th.copy_(self._acq_ties[:1 + nt])
-                packed = sorted(v & 0xFFFFFFFFFFFFFFFF
-                                for v in th[1:].tolist())
-                pk = random.choice(packed)
-                pos = pk >> 32
-                qv = struct.unpack(
-                    "<f", struct.pack("<I", pk & 0xFFFFFFFF))[0]
-            else:  # > buffer capacity: rescan (never seen in practice)
-                q = self._acq_qbuf
-                ties = (torch.isclose(q, q.max(), rtol=1e-8)
-                        & self._active_mask)
-                pos = random.choice(
-                    torch.nonzero(ties, as_tuple=True)[0].tolist())
-                qv = float(q[pos])
-            self.stochastic = True
-            return self._pairs_ids_host[pos], qv
-        return self._pairs_ids_host[bi], bv
-
-    def _init_acq_buffers(self):
-        if getattr(self, "_acq_out", None) is None:
-            ps, _ = self._pairs_static
-            self._pairs_ids_host = ps.cand_ids.cpu().tolist()
-            self._acq_out = torch.zeros(3, dtype=torch.float64,
-                                        device=self.device)
-            self._acq_qbuf = torch.empty(ps.cand_ids.numel(),
-                                         device=self.device)
-            # fused-epilogue tie buffer: [0]=slot counter, [1:] packs
-            # (position << 32) | q-value-bits per tie (host-sorted back
-            # to ascending position - one D2H fetch serves both the
-            # seeded tie-break AND its q value); overflow falls back to
-            # the full-scan path.  Host mirrors are PINNED so the
-            # per-step result fetches take the fast DMA path.
-            self._acq_ties = torch.zeros(8192, dtype=torch.int64,
-                                         device=self.device)
-            self._acq_out_host = torch.empty(
-                3, dtype=torch.float64, pin_memory=True)
-            self._acq_ties_host = torch.empty(
-                8192, dtype=torch.int64, pin_memory=True)
+        idx, q, tied = self._pair_acq.result()
+        self.stochastic |= tied
+        return idx, q
 
     def _acq_eligible(self) -> bool:
-        return (self.q == "eig" and self._pairs_static is not None
-                and self._pairs_static[0].vmask is not None
+        return (self.q == "eig" and self._pair_acq is not None
+                and self._pair_acq.ps.vmask is not None
                 and not DEBUG_VIZ
                 and not (self.prefilter_n
                          and len(self._active_candidates)
@@ -679,33 +621,20 @@ class CODA(ModelSelector):
 
     def _graphed_acquire(self):
         if self._acq_graph is None:
-            self._init_acq_buffers()
             self._sync_pair_cache()    # outside the capture
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._acq_body()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            first = self._acq_result()  # before capture rebinds _acq_q
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._acq_body()
-            self._acq_graph = g
+            self._acq_graph, first = _warm_and_capture(self._acq_body,
+                                                       self._acq_result)
             return first
         self._acq_graph.replay()
         return self._acq_result()
 
     # ------------------------------------------------------------------
     def get_next_item_to_label(self):
-        if getattr(self, "_acq_fresh", False) and self._acq_eligible():
+        pending, self._acq_pending = self._acq_pending, None
+        if pending is not None and self._acq_eligible():
             # the merged label+acquire graph already computed this
             # step's EIG/argmax during add_label
-            self._acq_fresh = False
-            if getattr(self, "_acq_saved", None) is not None:
-                res, self._acq_saved = self._acq_saved, None
-                return res
-            return self._acq_result()
+            return self._acq_result() if pending is _ON_DEVICE else pending
         if (self.q == "eig" and self._use_label_graph
                 and self._label_graph is not None
                 and self._acq_eligible()):
@@ -745,93 +674,69 @@ class CODA(ModelSelector):
              n_ties.double()]).cpu().tolist()
         bi, nt = int(bi), int(nt)
         if nt > 1:
-            ties = torch.isclose(q_vals, best_val, rtol=1e-8)
-            idx_local = random.choice(
-                torch.nonzero(ties, as_tuple=True)[0].tolist())
+            idx_local = tied_choice(q_vals, best_val)
             self.stochastic = True
             return cand[idx_local], float(q_vals[idx_local])
         return cand[int(bi)], bv
 
-    # -- hipGraph label-update pipeline --------------------------------
-    def _label_update_body(self):
-        """The tensor part of add_label as static-shape ops on the static
-        input buffers self._g_idx / self._g_y (both (1,) int64). Writes
-        tables in place and leaves the updated posterior rows in
-        self._g_rows. Captured once into a hipGraph; identical math to
-        the eager path (it IS the eager path, replayed)."""
+    # -- label update --------------------------------------------------
+    def _posterior_update(self, y_t, col):
+        """The part of a label update every path shares, on the (1,)
+        int64 class tensor y_t and the labeled point's (Hl,) argmax
+        classes: Dirichlet row add (K13), the exact rank-1 pi_hat
+        increment with its row sums (only Dirichlet row y moved),
+        all-reduced over shards, and the renormalized marginal, which is
+        returned. Static shapes, y read on the device: it captures."""
         lr = self.update_strength
-        idx_t, y_t = self._g_idx, self._g_y
-        col = self.classes.index_select(1, idx_t).squeeze(1)     # (Hl,)
-        if self.dirichlets.is_cuda and ops.hip_available():
+        on_hip = self.dirichlets.is_cuda and ops.hip_available()
+        if on_hip:
             # H-thread scatter: torch's one_hot + dim-1 index_add_ on the
             # (H,C,C) posterior costs ~914 us for H real nonzeros
+            # (matters on the eager path the distributed ranks take too)
             ops._ext.dirichlet_add(self.dirichlets, y_t, col, float(lr))
         else:
             onehot = torch.nn.functional.one_hot(col, self.C).to(
                 self.dirichlets.dtype)
             self.dirichlets.index_add_(1, y_t, (lr * onehot).unsqueeze(1))
         delta = ops.pi_hat_delta(self.dataset.preds, col,
-                                 preds_t=self._preds_t) * lr     # (N,)
-        if self._adjusted.is_cuda and ops.hip_available():
+                                 preds_t=self._preds_t)          # (N,)
+        if self.comm.is_distributed:    # never under capture
+            self.comm.all_reduce_(delta)
+        delta = delta * lr
+        if on_hip:
             # fused column update (torch index_add_ over dim 1 with one
             # index runs ~90x slower than this elementwise pass)
             ops._ext.col_add(self._adjusted, self._row_sums, y_t, delta)
         else:
             self._adjusted.index_add_(1, y_t, delta.unsqueeze(1))
             self._row_sums += delta
-        if self.C <= 2048 and ops.hip_available():
-            pi = ops._ext.pi_marginal(self._adjusted, self._row_sums)
-        else:
-            pi = (1.0 / self._row_sums.clamp_min(1e-12)) @ self._adjusted
-        self._g_pi.copy_(pi / pi.sum())
-        # refresh the labeled class's table row (v2 tables)
-        if self._tables is not None:
-            t = self._tables
-            if (t.eg16 is not None and t.egw is not None
-                    and t.delta16 is not None and t.dall is not None
-                    and ops.hip_available()):
-                # one fused commit (trc_* kernels in pbest.hip): the
-                # torch chain below was ~14 in-graph launches incl. two
-                # 32-thread strided reductions (10-24 us each)
-                a_col, b_col = ops._ext.table_commit_row(
-                    self.dirichlets, y_t, t.EG, t.delta, t.s_base,
-                    t.weights, t.eg16, t.egw, t.delta16, t.dall, 1.0)
-            else:
-                row = self.dirichlets.index_select(1, y_t) \
-                    .squeeze(1)                            # (Hl, C)
-                a_col = row.gather(
-                    1, y_t.view(1, 1).expand(self.Hl, 1)) \
-                    .squeeze(1).contiguous()
-                b_col = (row.sum(1) - a_col).contiguous()
-                eg, lc = ops._ext.beta_row_tables(a_col, b_col, 1.0)
-                t.EG.index_copy_(0, y_t, eg.unsqueeze(0))
-                if t.eg16 is not None:
-                    t.eg16.index_copy_(
-                        0, y_t, eg.reshape(1, 2 * self.Hl, -1)
-                        .to(torch.bfloat16))
-                t.delta.index_copy_(0, y_t,
-                                    (lc[:, 1] - lc[:, 0]).unsqueeze(0))
-                t.s_base.index_copy_(0, y_t, lc[:, 0].sum(0).unsqueeze(0))
-                if t.dall is not None:
-                    t.dall.index_copy_(
-                        0, y_t, t.delta.index_select(0, y_t).sum(1))
-                if t.egw is not None:
-                    esb = torch.exp2(t.s_base.index_select(0, y_t)) \
-                        * t.weights                         # (1, P)
-                    t.egw.index_copy_(
-                        0, y_t, (eg.reshape(1, 2 * self.Hl, -1)
-                                 * esb.unsqueeze(1)).to(torch.bfloat16))
-                    t.delta16.index_copy_(
-                        0, y_t, t.delta.index_select(0, y_t)
-                        .to(torch.float16))
-            if self._pair_cache is not None:
-                # class y's table rows just moved: re-evaluate its run
-                # of pairs (commit -> refresh -> entropy pass, in stream
-                # order; y is read on the device, so this captures)
-                from ..ops import pair as pops
-                ps, cls_rows = self._pairs_static
-                pops.pair_cache_refresh(self._pair_cache, t, ps, cls_rows,
-                                        y_t)
+        return self._pi_marginal()
+
+    # Two ways to finish a label, on purpose. Captured (single device):
+    # the tables are committed in-stream from the Dirichlets and the
+    # posterior row is computed from the columns the commit kernel
+    # returns. Eager (distributed ranks, graph-disabled runs, CPU): the
+    # class is marked dirty for a lazy table_update_rows and the row
+    # comes from torch sums over the Dirichlets or the replicated view.
+    # The columns agree only to the last bits, so merging the two would
+    # move the distributed trajectories.
+    def _graph_label_update(self):
+        """The tensor part of add_label as static-shape ops on the static
+        input buffers self._g_idx / self._g_y (both (1,) int64). Writes
+        tables in place and leaves the updated posterior rows in
+        self._g_rows. Captured once into a hipGraph."""
+        y_t = self._g_y
+        col = self.classes.index_select(1, self._g_idx).squeeze(1)  # (Hl,)
+        self._g_pi.copy_(self._posterior_update(y_t, col))
+        a_col, b_col = tops.table_commit_row(self._tables, self.dirichlets,
+                                             y_t)
+        acq = self._pair_acq
+        if acq is not None and acq.cache is not None:
+            # class y's table rows just moved: re-evaluate its run of
+            # pairs (commit -> refresh -> entropy pass, in stream order;
+            # y is read on the device, so this captures)
+            pops.pair_cache_refresh(acq.cache, self._tables, acq.ps,
+                                    acq.cls_rows, y_t)
         # posterior rows: add_label moves only Dirichlet row y, so only
         # class y's Beta column - hence only pbest row y - changes.
         # _g_rows was seeded with the full (C, Hl) rows at graph init;
@@ -842,8 +747,9 @@ class CODA(ModelSelector):
                                      self.num_points)        # (1, Hl)
         self._g_rows.index_copy_(0, y_t, rows_y)
 
-    def _graphed_add_label(self, idx: int, true_class: int):
-        if self._label_graph is None:
+    def _graphed_add_label(self, idx: int, y: int):
+        first = self._label_graph is None
+        if first:
             self._sync_pair_cache()    # outside the capture
             self._acq_graph = None     # captured on the buffers below
             self._g_idx = torch.zeros(1, dtype=torch.long,
@@ -853,104 +759,46 @@ class CODA(ModelSelector):
             # seeded with the PRE-label rows; the graph body refreshes
             # only the labeled class's row per replay
             self._g_rows = self._pbest_rows_before().clone().contiguous()
-            self._g_idx.fill_(idx)
-            self._g_y.fill_(true_class)
             # When the full-pool pair acquisition is active, the NEXT
             # step's acquisition is captured INTO the label graph: one
             # replay per step computes posterior update + next EIG +
             # argmax (the caller's get_next just reads the result).
             self._merged_acq = self._acq_eligible()
-            if self._merged_acq:
-                self._init_acq_buffers()
-
+        self._g_idx.fill_(idx)
+        self._g_y.fill_(y)
+        pending = _ON_DEVICE
+        if first:
             def body():
-                self._label_update_body()
+                self._graph_label_update()
                 if self._merged_acq:
                     self._acq_body()
 
-            # warmup executes the body for real (THIS label's update) on
-            # a side stream, as stream capture requires; the capture pass
-            # then only RECORDS the ops (no execution, no state change),
-            # so the first label must not additionally replay.
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                body()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            if self._merged_acq:
-                # the warmup's acquisition result serves the next
-                # get_next (capture below records without executing)
-                self._acq_saved = self._acq_result()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                body()
-            self._label_graph = g
-            self.pi_hat = self._g_pi
-            self._pbest_rows_cache = (self._posterior_version + 1,
-                                      self._g_rows)
-            self._acq_fresh = self._merged_acq
-            return
-        self._g_idx.fill_(idx)
-        self._g_y.fill_(true_class)
-        self._label_graph.replay()
+            # the warm-up applies THIS label's update, so the first
+            # label does not replay; its acquisition result, read before
+            # the capture, serves the next get_next
+            self._label_graph, pending = _warm_and_capture(
+                body, self._acq_result if self._merged_acq else None)
+        else:
+            self._label_graph.replay()
         self.pi_hat = self._g_pi
+        self._pi_xi_cache = None
         self._pbest_rows_cache = (self._posterior_version + 1,
                                   self._g_rows)
-        self._acq_fresh = self._merged_acq
+        self._acq_pending = pending if self._merged_acq else None
 
-    def add_label(self, idx, true_class, selection_prob):
-        """Posterior update (K13) + incremental pi_hat refresh.
-
-        Reference semantics (coda/coda.py:315-323); the pi_hat refresh is
-        the exact rank-1 increment (only Dirichlet row `true_class`
-        moved), all-reduced over shards. On single-device GPU the whole
-        tensor pipeline replays as one hipGraph."""
-        idx = int(idx)
-        if (self._use_label_graph and self._tables is not None
-                and not self._tables_dirty):
-            # the candidate mask update must be enqueued BEFORE the
-            # replay: the merged graph's acquisition half reads it
-            self._deactivate(idx)
-            self._graphed_add_label(idx, int(true_class))
-            self._posterior_version += 1
-            self._pi_xi_cache = None
-            self.labeled_idxs.append(idx)
-            self.labels.append(int(true_class))
-            self.q_vals.append(selection_prob)
-            self.unlabeled_idxs.remove(idx)
-            return
-        if self.dirichlets.is_cuda and ops.hip_available():
-            # H-thread scatter kernel; torch's one_hot + dim-1 index_add_
-            # on (H, C, C) costs ~915 us (matters on the eager path the
-            # distributed ranks take - no hipGraph under collectives)
-            y_t = torch.tensor([int(true_class)], dtype=torch.long,
-                               device=self.device)
-            ops._ext.dirichlet_add(self.dirichlets, y_t,
-                                   self.classes[:, idx].contiguous(),
-                                   float(self.update_strength))
-        else:
-            onehot = torch.nn.functional.one_hot(
-                self.classes[:, idx], self.C).to(self.dirichlets.dtype)
-            self.dirichlets[:, int(true_class)] += \
-                self.update_strength * onehot
+    def _eager_add_label(self, idx: int, y: int):
+        y_t = torch.tensor([y], dtype=torch.long, device=self.device)
+        self.pi_hat = self._posterior_update(
+            y_t, self.classes[:, idx].contiguous())
+        self._pi_xi_cache = None
         if self._replicated:
             # keep the replicated global Beta view current - a local
             # elementwise update from the (gathered-once) global classes,
             # identical on every rank, no collective
-            hit = self.classes_global[:, idx].long() == int(true_class)
-            self._alpha_g[:, int(true_class)] += \
-                self.update_strength * hit.float()
-            self._beta_g[:, int(true_class)] += \
-                self.update_strength * (~hit).float()
-        self._tables_dirty.add(int(true_class))
-        self._posterior_version += 1
-        delta = ops.pi_hat_delta(self.dataset.preds, self.classes[:, idx],
-                                 preds_t=self._preds_t)
-        self.comm.all_reduce_(delta)
-        self._adjusted[:, int(true_class)] += self.update_strength * delta
-        self._row_sums += self.update_strength * delta
-        self._refresh_pi_hat()
+            hit = self.classes_global[:, idx].long() == y
+            self._alpha_g[:, y] += self.update_strength * hit.float()
+            self._beta_g[:, y] += self.update_strength * (~hit).float()
+        self._tables_dirty.add(y)
         # incremental posterior rows on the EAGER path too (the
         # distributed ranks and graph-disabled runs): only class y's
         # Beta column moved, so refresh one row instead of the full
@@ -959,9 +807,8 @@ class CODA(ModelSelector):
         # holds the full model axis (single device or replicated mode);
         # the H-sharded v2 path keeps the sharded recompute.
         ver, cached = self._pbest_rows_cache
-        if (cached is not None and ver == self._posterior_version - 1
+        if (cached is not None and ver == self._posterior_version
                 and (self._replicated or not self.comm.is_distributed)):
-            y = int(true_class)
             if self._replicated:
                 a_col = self._alpha_g[:, y].contiguous()
                 b_col = self._beta_g[:, y].contiguous()
@@ -973,23 +820,39 @@ class CODA(ModelSelector):
             rows[y] = ops.pbest_from_beta(
                 a_col.unsqueeze(0), b_col.unsqueeze(0),
                 self.num_points)[0]
-            self._pbest_rows_cache = (self._posterior_version, rows)
+            self._pbest_rows_cache = (self._posterior_version + 1, rows)
+
+    def add_label(self, idx, true_class, selection_prob):
+        """Posterior update (K13) + incremental pi_hat refresh.
+
+        Reference semantics (coda/coda.py:315-323). On single-device GPU
+        the whole tensor pipeline replays as one hipGraph."""
+        idx, y = int(idx), int(true_class)
+        # the candidate mask update must be enqueued BEFORE the replay:
+        # the merged graph's acquisition half reads it
+        self._deactivate(idx)
+        if (self._use_label_graph and self._tables is not None
+                and not self._tables_dirty):
+            self._graphed_add_label(idx, y)
+        else:
+            self._eager_add_label(idx, y)
+        self._posterior_version += 1
         self.labeled_idxs.append(idx)
-        self.labels.append(int(true_class))
+        self.labels.append(y)
         self.q_vals.append(selection_prob)
         self.unlabeled_idxs.remove(idx)
-        self._deactivate(idx)
 
     def _deactivate(self, idx: int):
-        """Remove a point from the candidate pool (labeled or skipped)."""
+        """Remove a point from the candidate pool (labeled or skipped).
+        An acquisition computed before that may select it: a pending
+        result is dropped here, for every caller."""
+        self._acq_pending = None
         try:
             self._active_candidates.remove(idx)
         except ValueError:
             pass  # point was not a disagreeing candidate
-        if self._pair_row_of is not None:
-            row = self._pair_row_of.get(idx)
-            if row is not None:
-                self._active_mask[row] = False
+        if self._pair_acq is not None:
+            self._pair_acq.deactivate(idx)
 
     def skip(self, idx):
         """Drop a point without labeling it (the demo's "I don't know"
@@ -998,7 +861,6 @@ class CODA(ModelSelector):
         if idx in self.unlabeled_idxs:
             self.unlabeled_idxs.remove(idx)
         self._deactivate(idx)
-        self._acq_fresh = False  # precomputed EIG predates the skip
 
     # ------------------------------------------------------------------
     def get_pbest(self):

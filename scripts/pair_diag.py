@@ -97,4 +97,4 @@ for _ in range(4):
     sel.add_label(i, oracle2(int(i)), q)
     sel.get_best_model_prediction()
 print("label graph live:", sel._label_graph is not None,
-      "impl pair static:", sel._pairs_static is not None)
+      "impl pair static:", sel._pair_acq is not None)

@@ -189,14 +189,14 @@ class TestPairEig:
         torch.manual_seed(0)
         sel = CODA(ds, eig_impl="pair")
         i0, q0 = sel.get_next_item_to_label()
-        assert sel._pairs_static is not None
-        ps0 = sel._pairs_static[0]
+        assert sel._pair_acq is not None
+        ps0 = sel._pair_acq.ps
         sel.add_label(i0, oracle(int(i0)), q0)
         i1, _ = sel.get_next_item_to_label()
-        assert sel._pairs_static[0] is ps0, "structure rebuilt"
+        assert sel._pair_acq.ps is ps0, "structure rebuilt"
         assert int(i1) != int(i0), "labeled point re-selected"
-        row = sel._pair_row_of[int(i0)]
-        assert not bool(sel._active_mask[row])
+        row = sel._pair_acq.row_of[int(i0)]
+        assert not bool(sel._pair_acq.active[row])
 
     def test_skip_removes_candidate(self):
         preds, labels = make_synthetic_task(H=8, N=150, C=5, seed=5)

@@ -167,11 +167,11 @@ class TestCpuSelector:
         prev, moved = None, []
         for _ in range(4):
             i, q = sel.get_next_item_to_label()
-            ps, cls_rows = sel._pairs_static
-            cache = sel._pair_cache
+            ps, cls_rows = sel._pair_acq.ps, sel._pair_acq.cls_rows
+            cache = sel._pair_acq.cache
             assert ps.cand_ids.numel() >= 4096 and ps.tile == 128
             assert cache is not None and cache.pbn is not None
-            assert cache.pm is None and not sel._pair_cache_stale
+            assert cache.pm is None and not sel._pair_acq.stale
             torch.testing.assert_close(
                 cache.pbn, pops.pair_pbn(sel._tables, ps, cls_rows),
                 rtol=0, atol=1e-6)
@@ -190,7 +190,8 @@ class TestCpuSelector:
     def test_env_switch_and_invalidation(self, monkeypatch,
                                          synthetic_dataset, tmp_path):
         """CODA_AMD_NO_PAIR_CACHE=1 and a pool under the gate both leave
-        the cache absent; a checkpoint restore drops it."""
+        the cache absent; a checkpoint restore drops it, and leaves
+        every derived field as a fresh selector has it."""
         from coda_amd import CODA, checkpoint
         monkeypatch.setenv("CODA_AMD_NO_PAIR_CACHE", "1")
         assert not CODA(synthetic_dataset)._use_pair_cache
@@ -198,12 +199,124 @@ class TestCpuSelector:
         sel = CODA(synthetic_dataset, eig_impl="pair")
         assert sel._use_pair_cache
         i, q = sel.get_next_item_to_label()
-        assert sel._pairs_static[0].tile == 16
-        assert sel._pair_cache is None and sel._pair_cache_declined
-        sel._pair_cache = object()          # stand-in: restore must drop it
+        acq = sel._pair_acq
+        assert acq.ps.tile == 16
+        assert acq.cache is None and acq.declined
+        acq.cache = object()                # stand-in: restore must drop it
         path = checkpoint.save(sel, str(tmp_path / "c.pt"))
         checkpoint.load(sel, path)
-        assert sel._pair_cache is None and not sel._pair_cache_declined
+        assert sel._pair_acq is None
+        # nothing was labelled, so the restored state is the initial
+        # one: every private field, whatever later changes add, equals
+        # a fresh selector's
+        fresh = CODA(synthetic_dataset, eig_impl="pair")
+        assert vars(sel).keys() == vars(fresh).keys()
+        for name, want in vars(fresh).items():
+            if name.startswith("_"):
+                assert _same_value(getattr(sel, name), want), name
+
+    @pytest.fixture(scope="class")
+    def restored_run(self, tmp_path_factory):
+        """(uninterrupted 7-step selector, the one saved after 3 steps,
+        a fresh one restored from it and run 4 further steps)."""
+        from coda_amd import CODA, checkpoint
+        ds, oracle = G._pool("cpu", 6000)
+
+        def fresh():
+            random.seed(0)
+            torch.manual_seed(0)
+            return CODA(ds, eig_impl="pair")
+
+        def steps(sel, n):
+            for _ in range(n):
+                i, q = sel.get_next_item_to_label()
+                sel.add_label(i, oracle(int(i)), q)
+
+        with pytest.MonkeyPatch.context() as mp:
+            mp.delenv("CODA_AMD_NO_PAIR_CACHE", raising=False)
+            whole = fresh()
+            steps(whole, 7)
+            saved = fresh()
+            steps(saved, 3)
+            rng = random.getstate()
+            path = checkpoint.save(
+                saved, str(tmp_path_factory.mktemp("ckpt") / "s.pt"))
+            restored = checkpoint.load(fresh(), path)
+            assert restored._pair_acq is None and restored._tables is None
+            random.setstate(rng)
+            steps(restored, 4)
+        return whole, saved, restored
+
+    def test_restore_rebuilds_every_derived_object(self, restored_run):
+        """Three steps, save, load into a fresh selector, four further
+        steps: the restored selector shares no derived object with the
+        saved one (structure, cache and mask are rebuilt) and labels
+        the points the uninterrupted run labels."""
+        whole, saved, restored = restored_run
+        assert restored.labeled_idxs == whole.labeled_idxs
+        assert restored._pair_acq.cache is not None
+        derived = {**_objects(saved._pair_acq), **_objects(saved._tables),
+                   **_objects(saved._pbest_rows_cache)}
+        acq = saved._pair_acq
+        for o in (acq.ps.pair_c, acq.cls_rows, acq.active, acq.row_of,
+                  acq.cache.pbn, saved._tables.EG):
+            assert id(o) in derived     # the walk reaches what matters
+        shared = [name for name, v in vars(restored).items()
+                  if _objects(v).keys() & derived.keys()]
+        assert not shared, shared
+
+    def test_restore_continues_q_vals_bitwise(self, restored_run):
+        """...and reproduces the uninterrupted run's q_vals bit for bit:
+        the checkpoint carries the pi_hat accumulators. (Recomputed by
+        the full contraction they come out 5.7e-6 off the sum of the
+        rank-1 increments here, and q 1e-7 off.)"""
+        whole, _, restored = restored_run
+        assert ([float(v) for v in restored.q_vals]
+                == [float(v) for v in whole.q_vals])
+
+    def test_checkpoint_without_accumulators_still_loads(self,
+                                                         restored_run):
+        """A checkpoint written before the accumulators were saved
+        restores through the full contraction. (Each entry is a sum of
+        H*C = 36 positive fp32 terms plus three increments, so either
+        order of summation is within ~40 * 2^-24 = 2.4e-6 relative of
+        the exact sum: 1e-5 between the two.)"""
+        from coda_amd import CODA, checkpoint
+        _, saved, _ = restored_run
+        state = checkpoint.state_dict(saved)
+        want = state["_adjusted"]
+        del state["_adjusted"], state["_row_sums"]
+        sel = checkpoint.load_state_dict(
+            CODA(saved.dataset, eig_impl="pair"), state)
+        torch.testing.assert_close(sel._adjusted, want, rtol=1e-5, atol=0)
+        torch.testing.assert_close(sel.pi_hat, saved.pi_hat, rtol=1e-5,
+                                   atol=0)
+
+
+def _same_value(a, b):
+    if torch.is_tensor(a) or torch.is_tensor(b):
+        return (torch.is_tensor(a) and torch.is_tensor(b)
+                and torch.equal(a, b))
+    if isinstance(a, tuple):
+        return (isinstance(b, tuple) and len(a) == len(b)
+                and all(map(_same_value, a, b)))
+    return a == b
+
+
+def _objects(v, depth=3):
+    """{id: object} of the tensors, mutable containers and class
+    instances reachable from a value, a few levels down. (Tuples are
+    looked through, not recorded: equal constants share one object.)"""
+    if v is None or isinstance(v, (bool, int, float, str)):
+        return {}
+    out = {} if isinstance(v, tuple) else {id(v): v}
+    if depth and not torch.is_tensor(v):
+        kids = (v if isinstance(v, (tuple, set))
+                else v.values() if isinstance(v, dict)
+                else vars(v).values() if hasattr(v, "__dict__") else ())
+        for k in kids:
+            out.update(_objects(k, depth - 1))
+    return out
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
