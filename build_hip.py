@@ -19,6 +19,7 @@ SRC = [os.path.join(REPO, "coda_amd", "ops", "hip", "pbest.hip"),
        os.path.join(REPO, "coda_amd", "ops", "hip", "pair.hip"),
        os.path.join(REPO, "coda_amd", "ops", "hip", "ingest.hip"),
        os.path.join(REPO, "coda_amd", "ops", "hip", "ingest_f16.hip"),
+       os.path.join(REPO, "coda_amd", "ops", "hip", "ingest_logits.hip"),
        os.path.join(REPO, "coda_amd", "ops", "hip", "modelpicker.hip")]
 # headers the sources include: part of the up-to-date check only
 HDR = [os.path.join(REPO, "coda_amd", "ops", "hip", "ingest_kernel.h")]

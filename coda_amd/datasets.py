@@ -26,11 +26,23 @@ Additions over the reference:
     `Dataset(<dir or manifest>)` streams it chunk by chunk in the file's
     own dtype through the fused ingest op (ops.ingest_chunk) - see
     Dataset._init_sharded; `write_sharded_task` writes it.
+  - logit pools, in the sharded format only: a manifest with
+      "format": "coda_amd.shards/2", "kind": "logits",
+      "temperature": T | [T_0, ..., T_{H-1}]        (optional, default 1)
+    holds pre-softmax logits (fp32 / fp16 / bf16; entries finite or -inf,
+    at least one finite per row). The ingest op applies the per-model
+    temperature softmax softmax(x / T_h) in the same pass, so the loaded
+    `Dataset` is an ordinary probability pool and `Dataset(...,
+    temperature=)` re-tempers at load time without rewriting the file.
+    The format number moves so that a build that predates logits refuses
+    such a task instead of reading logits as probabilities. `.pt` files
+    and `Dataset.from_tensors` are probability-only.
 """
 from __future__ import annotations
 
 import json
 import os
+import math
 from typing import Optional, Tuple
 
 import torch
@@ -49,15 +61,26 @@ WIRE_DTYPES = dict(STORAGE_DTYPES)
 # for; an fp16 tensor is up-cast there, like an fp16 file by default
 _KEPT_DTYPES = (torch.float32, torch.bfloat16, torch.float8_e4m3fn)
 SHARD_FORMAT = "coda_amd.shards/1"
+# logits tasks: same layout plus "kind" and an optional "temperature"
+SHARD_FORMAT_LOGITS = "coda_amd.shards/2"
+SHARD_FORMATS = (SHARD_FORMAT, SHARD_FORMAT_LOGITS)
+TASK_KINDS = ("probs", "logits")
+LOGIT_WIRE_DTYPES = ("fp32", "fp16", "bf16")
 MANIFEST_NAME = "manifest.json"
 
 
 class Dataset:
+    # what the task file held; a logits task also records the (H,) fp64
+    # temperatures its softmax was taken at (global model ids)
+    kind = "probs"
+    temperature = None
+
     def __init__(self, filepath: str, device,
                  shard: Optional[Tuple[int, int]] = None,
                  pin: bool = False,
                  storage_dtype: str = "fp32",
-                 stream_chunk_mb: int = 0):
+                 stream_chunk_mb: int = 0,
+                 temperature=None):
         """Load a prediction tensor.
 
         Args:
@@ -82,12 +105,21 @@ class Dataset:
             stream_chunk_mb: >0 streams the tensor host->device in chunks
                 of this size through pinned buffers on a side stream
                 (dtype conversion on device), instead of one blocking copy.
+            temperature: softmax temperature of a sharded LOGITS task
+                (manifest "kind": "logits"): one positive number or one
+                per model (length H, global model ids whatever `shard`
+                is). Overrides the manifest's value; default is the
+                manifest's, else 1. A ValueError for a probability task
+                (sharded or .pt), whose softmax is already in the file.
         """
         self.device = torch.device(device)
         if _is_sharded_path(filepath):
             self._init_sharded(filepath, shard, storage_dtype,
-                               stream_chunk_mb)
+                               stream_chunk_mb, temperature)
             return
+        if temperature is not None:
+            raise ValueError("temperature applies to sharded logits tasks "
+                             f"only; {filepath} holds probabilities")
         preds = torch.load(filepath, map_location="cpu", weights_only=True)
         dt = STORAGE_DTYPES[storage_dtype]
         # an fp16 file bound for fp16 storage stays fp16 on the host, on
@@ -115,7 +147,8 @@ class Dataset:
             labels = torch.load(label_p, map_location="cpu", weights_only=True)
             self.labels = labels.to(self.device)
 
-    def _init_sharded(self, path, shard, storage_dtype, stream_chunk_mb):
+    def _init_sharded(self, path, shard, storage_dtype, stream_chunk_mb,
+                      temperature=None):
         """Load a `<task>.shards/` directory (format: module docstring).
 
         The host never holds more than two chunks, in the file's own
@@ -126,7 +159,13 @@ class Dataset:
         on that stream - one fused pass that rounds to the storage dtype
         and produces the selector's init statistics (`init_stats`) and,
         HBM headroom permitting, the class-major mirror. On a CPU device
-        the same loop runs with the eager twin."""
+        the same loop runs with the eager twin.
+
+        A logits task (manifest "kind": "logits") takes the same route
+        with the same host footprint: every chunk carries its models'
+        k_h = float32(log2(e) / T_h) and the ingest pass applies the
+        temperature softmax before rounding, so everything downstream
+        sees a probability pool."""
         from . import ops
         from .util import mirror_fits
 
@@ -142,6 +181,25 @@ class Dataset:
         self.model_idxs = torch.arange(rank, H, world)
         self.storage_dtype = storage_dtype
         Hl = self.model_idxs.numel()
+        logits = man["kind"] == "logits"
+        self.kind = man["kind"]
+        self.temperature = None
+        scale = None
+        if logits:
+            if temperature is None:
+                temperature = man["temperature"]
+            temps = _check_temperature(
+                1.0 if temperature is None else temperature, H,
+                "temperature")
+            if len(temps) == 1:
+                temps = temps * H
+            # by GLOBAL model id; k_h rounded once, from fp64
+            self.temperature = torch.tensor(temps, dtype=torch.float64)
+            scale = ((math.log2(math.e) / self.temperature)
+                     .to(torch.float32)[self.model_idxs].to(dev))
+        elif temperature is not None:
+            raise ValueError("temperature applies to logits tasks only; "
+                             f"{path} holds probabilities")
 
         esize = torch.empty(0, dtype=wire_dt).element_size()
         budget = max(1, int((stream_chunk_mb or 256) * (1 << 20)))
@@ -187,9 +245,10 @@ class Dataset:
                 for n0 in range(0, N, npts):
                     n1 = min(n0 + npts, N)
                     src = t[a:b:world, n0:n1]
+                    k_h = scale[la:lb] if logits else None
                     if not on_gpu:
                         ops.ingest_chunk(src.contiguous(), la, n0, preds,
-                                         classes, ens, preds_t)
+                                         classes, ens, preds_t, k_h)
                         continue
                     k = i % 2
                     i += 1
@@ -199,11 +258,17 @@ class Dataset:
                     with torch.cuda.stream(side):
                         wire = stage.to(dev, non_blocking=True)
                         ops.ingest_chunk(wire, la, n0, preds, classes, ens,
-                                         preds_t)
+                                         preds_t, k_h)
                         events[k].record(side)
             del t
         if on_gpu:
             torch.cuda.current_stream(dev).wait_stream(side)
+        # the one guard against a logits file our writer did not check
+        # (a NaN / +inf entry or an all -inf row makes its row non-finite)
+        if logits and not bool(torch.isfinite(ens).all()):
+            raise ValueError(f"{path}: non-finite probabilities from a "
+                             "logits task (logits must be finite or -inf, "
+                             "with a finite entry in every row)")
 
         self.preds = preds
         self.init_stats = {"classes": classes, "ens_sum": ens,
@@ -263,20 +328,42 @@ def _is_sharded_path(path: str) -> bool:
     return os.path.isdir(path) or os.path.basename(path) == MANIFEST_NAME
 
 
-def read_shard_manifest(path: str) -> dict:
+def _check_temperature(t, H: int, what: str) -> list:
+    """One positive finite number, or a list of 1 or H of them -> list."""
+    if isinstance(t, torch.Tensor):
+        t = t.tolist()
+    vals = list(t) if isinstance(t, (list, tuple)) else [t]
+    if len(vals) not in (1, H):
+        raise ValueError(f"{what}: expected one value or one per model "
+                         f"({H}), got {len(vals)}")
+    out = []
+    for v in vals:
+        if (isinstance(v, bool) or not isinstance(v, (int, float))
+                or not math.isfinite(v) or v <= 0):
+            raise ValueError(f"{what}: {v!r} is not a positive finite "
+                             "number")
+        out.append(float(v))
+    return out
+
+
+def read_shard_manifest(path: str, formats=SHARD_FORMATS) -> dict:
     """Read and validate `<task>.shards/manifest.json` (path may be the
     directory or the manifest). Returns the manifest with a `root` key
-    (the directory); raises ValueError on an unknown format or dtype, or
-    shards that do not partition [0, H) in ascending order."""
+    (the directory) and `kind` / `temperature` filled in ("probs" / None
+    when absent); raises ValueError on an unknown format (one not in
+    `formats`), dtype or kind, a malformed temperature, or shards that do
+    not partition [0, H) in ascending order."""
     root = path if os.path.isdir(path) else os.path.dirname(path)
     mpath = os.path.join(root, MANIFEST_NAME)
     if not os.path.exists(mpath):
         raise FileNotFoundError(f"no {MANIFEST_NAME} in {root}")
     with open(mpath) as f:
         man = json.load(f)
-    if man.get("format") != SHARD_FORMAT:
+    formats = tuple(formats)
+    if man.get("format") not in formats:
+        want = formats[0] if len(formats) == 1 else f"one of {formats}"
         raise ValueError(f"{mpath}: unknown format {man.get('format')!r} "
-                         f"(expected {SHARD_FORMAT!r})")
+                         f"(expected {want!r})")
     if man.get("dtype") not in WIRE_DTYPES:
         raise ValueError(f"{mpath}: unknown dtype {man.get('dtype')!r} "
                          f"(expected one of {sorted(WIRE_DTYPES)})")
@@ -302,6 +389,26 @@ def read_shard_manifest(path: str) -> dict:
     if at != man["H"]:
         raise ValueError(f"{mpath}: shards cover [0, {at}) but H = "
                          f"{man['H']}")
+    if man["format"] == SHARD_FORMAT_LOGITS:
+        if man.get("kind") != "logits":
+            raise ValueError(f"{mpath}: format {SHARD_FORMAT_LOGITS!r} "
+                             f"needs \"kind\": \"logits\", got "
+                             f"{man.get('kind')!r}")
+        if man["dtype"] not in LOGIT_WIRE_DTYPES:
+            raise ValueError(f"{mpath}: logits in {man['dtype']} are not "
+                             f"supported (one of {LOGIT_WIRE_DTYPES})")
+        if man.get("temperature") is not None:
+            _check_temperature(man["temperature"], man["H"],
+                               f"{mpath}: temperature")
+    else:
+        if man.get("kind", "probs") != "probs":
+            raise ValueError(f"{mpath}: kind {man.get('kind')!r} needs "
+                             f"format {SHARD_FORMAT_LOGITS!r}")
+        if man.get("temperature") is not None:
+            raise ValueError(f"{mpath}: temperature applies to logits "
+                             "tasks only")
+    man.setdefault("kind", "probs")
+    man.setdefault("temperature", None)
     man.setdefault("labels", None)
     man["root"] = root
     return man
@@ -318,10 +425,33 @@ def _check_shard_tensor(t, sh, N, C, wire_dt):
                          f"match the manifest's {wire_dt}")
 
 
+def _check_logit_shard(out: torch.Tensor, name: str) -> None:
+    """Logits as written: finite or -inf, a finite entry in every row
+    (checked a model at a time: no shard-size fp32 transient)."""
+    for h in range(out.shape[0]):
+        x = out[h].float()
+        fin = torch.isfinite(x)
+        if bool((~fin & (x != float("-inf"))).any()):
+            raise ValueError(f"shard {name}: logits of model {h} of the "
+                             "shard hold NaN or +inf (entries must be "
+                             "finite or -inf)")
+        if not bool(fin.any(dim=-1).all()):
+            raise ValueError(f"shard {name}: model {h} of the shard has a "
+                             "row without a finite logit")
+
+
 def write_sharded_task(out_dir: str, shard_iter_or_tensor, dtype: str,
-                       models_per_shard: int = 16, labels=None) -> str:
+                       models_per_shard: int = 16, labels=None,
+                       kind: str = "probs", temperature=None) -> str:
     """Write a `<task>.shards/` directory in on-disk dtype `dtype`
     ("fp32" | "fp16" | "bf16" | "fp8").
+
+    kind="probs" (post-softmax scores) writes format coda_amd.shards/1 as
+    always. kind="logits" (fp32 / fp16 / bf16 only) writes format
+    coda_amd.shards/2 with "kind": "logits" and, when `temperature` is
+    given (one positive number or one per model), "temperature"; every
+    shard is checked as written - entries finite or -inf, a finite entry
+    in every row - and a violation raises ValueError naming the shard.
 
     The source is either one (H, N, C) tensor (an mmap'd one is fine: it
     is cut into `models_per_shard`-model slices, converted one at a time)
@@ -330,6 +460,14 @@ def write_sharded_task(out_dir: str, shard_iter_or_tensor, dtype: str,
     if dtype not in WIRE_DTYPES:
         raise ValueError(f"unknown dtype {dtype!r} "
                          f"(expected one of {sorted(WIRE_DTYPES)})")
+    if kind not in TASK_KINDS:
+        raise ValueError(f"unknown kind {kind!r} (expected one of "
+                         f"{TASK_KINDS})")
+    if kind == "logits" and dtype not in LOGIT_WIRE_DTYPES:
+        raise ValueError(f"logits in {dtype} are not supported (one of "
+                         f"{LOGIT_WIRE_DTYPES})")
+    if kind != "logits" and temperature is not None:
+        raise ValueError("temperature applies to kind=\"logits\" only")
     dt = WIRE_DTYPES[dtype]
     if isinstance(shard_iter_or_tensor, torch.Tensor):
         src = shard_iter_or_tensor
@@ -351,6 +489,8 @@ def write_sharded_task(out_dir: str, shard_iter_or_tensor, dtype: str,
         out = piece if piece.dtype == dt else piece.float().to(dt)
         h1 = at + int(piece.shape[0])
         name = f"h{at:06d}-{h1:06d}.pt"
+        if kind == "logits":
+            _check_logit_shard(out, name)
         # clone: a slice would drag its whole backing storage into the file
         torch.save(out.contiguous().clone(), os.path.join(out_dir, name))
         shards.append({"file": name, "h0": at, "h1": h1})
@@ -363,6 +503,12 @@ def write_sharded_task(out_dir: str, shard_iter_or_tensor, dtype: str,
         torch.save(labels.cpu().clone(), os.path.join(out_dir, label_name))
     man = {"format": SHARD_FORMAT, "H": at, "N": N, "C": C, "dtype": dtype,
            "shards": shards, "labels": label_name}
+    if kind == "logits":
+        man["format"] = SHARD_FORMAT_LOGITS
+        man["kind"] = "logits"
+        if temperature is not None:
+            temps = _check_temperature(temperature, at, "temperature")
+            man["temperature"] = temps[0] if len(temps) == 1 else temps
     mpath = os.path.join(out_dir, MANIFEST_NAME)
     with open(mpath, "w") as f:
         json.dump(man, f, indent=1)

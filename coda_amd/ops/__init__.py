@@ -70,18 +70,46 @@ def _want_hip(t: torch.Tensor) -> bool:
 def ingest_chunk(wire: torch.Tensor, h0: int, n0: int,
                  preds_out: torch.Tensor, classes_out: torch.Tensor,
                  ens_out: torch.Tensor,
-                 preds_t_out: torch.Tensor = None) -> None:
+                 preds_t_out: torch.Tensor = None,
+                 logit_scale: torch.Tensor = None) -> None:
     """Fused pool ingest of one wire-dtype chunk (contract:
     reference.ingest_chunk). On a ROCm device this is one gfx950 kernel
     pass (ingest.hip) that rounds to the storage dtype, takes the argmax
     classes, advances the consensus sum and optionally writes the
-    class-major mirror; all outputs are bit-equal to the eager twin."""
+    class-major mirror; all outputs are bit-equal to the eager twin.
+
+    logit_scale, an (hc,) fp32 tensor k_h = log2(e) / T_h on the wire's
+    device, declares the chunk to hold logits (fp32 / fp16 / bf16): the
+    pass (ingest_logits.hip) first takes the per-model temperature
+    softmax exp2((x - max x) * k_h) / Z in fp32. That pool is NOT
+    bit-equal to the eager twin - the hardware exp2 is a 1-ulp unit that
+    flushes results below 2^-126, and the twin sums Z in torch's order -
+    but close to it (PARITY.md, L2); classes, consensus and mirror are
+    exact functions of the pool the pass stored."""
+    if logit_scale is not None:
+        _check_logit_scale(wire, logit_scale)
     if _want_hip(preds_out):
+        if logit_scale is not None:
+            _ext.ingest_logits_chunk(wire, logit_scale, int(h0), int(n0),
+                                     preds_out, classes_out, ens_out,
+                                     preds_t_out)
+            return
         _ext.ingest_chunk(wire, int(h0), int(n0), preds_out, classes_out,
                           ens_out, preds_t_out)
         return
     reference.ingest_chunk(wire, h0, n0, preds_out, classes_out, ens_out,
-                           preds_t_out)
+                           preds_t_out, logit_scale)
+
+
+def _check_logit_scale(wire: torch.Tensor, k: torch.Tensor) -> None:
+    if wire.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise ValueError(f"logits wire dtype must be fp32/fp16/bf16, got "
+                         f"{wire.dtype}")
+    if (not isinstance(k, torch.Tensor) or k.dtype != torch.float32
+            or k.dim() != 1 or k.shape[0] != wire.shape[0]
+            or k.device != wire.device):
+        raise ValueError("logit_scale must be an (hc,) fp32 tensor on the "
+                         "wire's device")
 
 
 def modelpicker_dev(struct: ModelPickerStruct, posterior: torch.Tensor,

@@ -2414,12 +2414,14 @@ torch::Tensor pi_marginal(torch::Tensor adjusted, torch::Tensor row_sums) {
 
 void register_pair_ops(pybind11::module_& m);  // pair.hip (v3 engine)
 void register_ingest_ops(pybind11::module_& m);  // ingest.hip (pool ingest)
+void register_ingest_logits_ops(pybind11::module_& m);  // ingest_logits.hip
 void register_modelpicker_ops(pybind11::module_& m);  // modelpicker.hip
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.doc() = "coda_amd fused gfx950 kernels";
     register_pair_ops(m);
     register_ingest_ops(m);
+    register_ingest_logits_ops(m);
     register_modelpicker_ops(m);
     m.def("pbest_from_beta", &pbest_from_beta,
           "Beta-grid P(best) per row: (R,H),(R,H) -> (R,H)");

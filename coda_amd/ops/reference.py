@@ -89,7 +89,8 @@ def ensemble_mean(preds: torch.Tensor, chunk_n: int = 0) -> torch.Tensor:
 def ingest_chunk(wire: torch.Tensor, h0: int, n0: int,
                  preds_out: torch.Tensor, classes_out: torch.Tensor,
                  ens_out: torch.Tensor,
-                 preds_t_out: torch.Tensor = None) -> None:
+                 preds_t_out: torch.Tensor = None,
+                 logit_scale: torch.Tensor = None) -> None:
     """Fused pool ingest of one (hc, nc, C) wire-dtype chunk covering local
     models h0..h0+hc and points n0..n0+nc (eager twin of ingest.hip).
 
@@ -97,8 +98,23 @@ def ingest_chunk(wire: torch.Tensor, h0: int, n0: int,
     fp32: stores s into preds_out (and, class-major, into preds_t_out),
     the lowest-index argmax of f into classes_out, and advances ens_out by
     the plain left-to-right fp32 sum over h ascending - one add per model,
-    so the result does not depend on how the pool is chunked."""
+    so the result does not depend on how the pool is chunked.
+
+    With logit_scale, an (hc,) fp32 tensor k_h = log2(e) / T_h, the chunk
+    holds logits x (eager twin of ingest_logits.hip) and s is the storage
+    rounding of the temperature softmax, all in fp32:
+        m = max_c x[c];  e_c = exp2((x[c] - m) * k_h)   (-inf gives 0)
+        Z = sum_c e_c;   p_c = e_c / Z;   s_c = storage_round(p_c)
+    so every tied maximum has e = 1 and stores the same s. The kernel and
+    this twin are NOT bit-equal: the hardware exp2 is a 1-ulp unit that
+    may flush results below 2^-126 to zero, and the kernel sums Z in its
+    own fixed lane order. PARITY.md (L2) bounds the difference."""
     hc, nc, _ = wire.shape
+    if logit_scale is not None:
+        x = wire.float()
+        m = x.max(dim=-1, keepdim=True).values
+        e = torch.exp2((x - m) * logit_scale.view(hc, 1, 1))
+        wire = e / e.sum(dim=-1, keepdim=True)
     s = wire.float().to(preds_out.dtype)
     f = s.float()
     preds_out[h0:h0 + hc, n0:n0 + nc] = s

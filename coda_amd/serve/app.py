@@ -244,7 +244,7 @@ def create_app(dataset, method: str = "coda", oracle=None, seed: int = 0,
 def main():
     import argparse
     import uvicorn
-    from ..datasets import Dataset, STORAGE_DTYPES
+    from ..datasets import Dataset, STORAGE_DTYPES, resolve_task_path
     from ..oracle import Oracle
     from ..options import LOSS_FNS
 
@@ -258,14 +258,17 @@ def main():
     ap.add_argument("--storage", default="fp32",
                     choices=sorted(STORAGE_DTYPES),
                     help="on-device prediction-pool dtype")
+    ap.add_argument("--temperature", type=float, default=None,
+                    help="softmax temperature of a sharded logits task "
+                         "(an error for a probability task)")
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=7860)
     args = ap.parse_args()
 
     device = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
-    import os
-    ds = Dataset(os.path.join(args.data_dir, args.task + ".pt"), device,
-                 storage_dtype=args.storage)
+    # <data-dir>/<task>.pt first; <task>.shards/ only when that is missing
+    ds = Dataset(resolve_task_path(args.data_dir, args.task), device,
+                 storage_dtype=args.storage, temperature=args.temperature)
     oracle = Oracle(ds, LOSS_FNS["acc"]) if ds.labels is not None else None
     app = create_app(ds, method=args.method, oracle=oracle,
                      images_dir=args.images_dir)

@@ -103,6 +103,10 @@ def parse_args(argv=None):
                         help="Stream the pool host->HBM through pinned "
                              "buffers of this size (0 = one blocking copy; "
                              "sharded tasks always stream, 256 when 0).")
+    parser.add_argument("--temperature", type=float, default=None,
+                        help="Softmax temperature of a sharded logits task "
+                             "(overrides the manifest's; an error for a "
+                             "probability task).")
     parser.add_argument("--mp-entropy", default="auto",
                         choices=["auto", "dense", "sparse"],
                         help="ModelPicker expected-entropy path: the dense "
@@ -260,7 +264,8 @@ def main(argv=None):
     dataset = Dataset(resolve_task_path(args.data_dir, args.task),
                       device=device, shard=shard,
                       storage_dtype=args.storage,
-                      stream_chunk_mb=args.stream_chunk_mb)
+                      stream_chunk_mb=args.stream_chunk_mb,
+                      temperature=args.temperature)
     loss_fn = LOSS_FNS[args.loss]
     oracle = Oracle(dataset, loss_fn=loss_fn)
 
