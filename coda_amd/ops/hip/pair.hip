@@ -948,9 +948,11 @@ pair_entropy_wide_cls_kernel(const hip_bfloat16* __restrict__ m,  // (K, 2H)
 // B=50k): three kernels replace it.
 //   K1: qbuf = active ? h0 + q0 : -inf, per-block (max, first-idx)
 //   K2: one block combines the partials -> out[0..1]
-//   K3: tie count |q - best| <= atol + rtol*|best| over active
-//       candidates (torch.isclose semantics), f64 atomic into out[2]
-//       (integer-valued doubles: exact, order-independent)
+//   K3: tie count q == best, or |q - best| finite and <= atol +
+//       rtol*|best|, over active candidates (torch.isclose on finite
+//       and infinite values), f64 atomic into out[2] (integer-valued
+//       doubles: exact, order-independent)
+// The contract, as plain numpy, is tests/acq_ref.py.
 // ---------------------------------------------------------------------
 #define ACQ_GRID 256
 
@@ -968,9 +970,17 @@ acq_select_part_kernel(const float* __restrict__ q0,
     float best = -INFINITY;
     int bidx = -1;
     for (int i = b0 + threadIdx.x; i < b1; i += BLOCK) {
-        const float q = active[i] ? h + q0[i] : -INFINITY;
+        const bool a = active[i];
+        const float q = a ? h + q0[i] : -INFINITY;
         qbuf[i] = q;
-        if (q > best) { best = q; bidx = i; }   // strict: first index wins
+        // strict: first index wins.  The first active candidate seeds
+        // (best, bidx) even at -inf, so an all -inf active set yields its
+        // first index, not -1.  NaN compares false both ways and is
+        // skipped, unlike the eager chain, whose max propagates it.
+        if (a && (q > best || (bidx < 0 && q == best))) {
+            best = q;
+            bidx = i;
+        }
     }
     __shared__ float sv[BLOCK];
     __shared__ int si[BLOCK];
@@ -1039,8 +1049,14 @@ acq_select_ties_kernel(const float* __restrict__ qbuf,
     const int b0 = blockIdx.x * per;
     const int b1 = min(b0 + per, B);
     int cnt = 0;
-    for (int i = b0 + threadIdx.x; i < b1; i += BLOCK)
-        if (active[i] && fabsf(qbuf[i] - best) <= thr) {
+    for (int i = b0 + threadIdx.x; i < b1; i += BLOCK) {
+        if (!active[i]) continue;
+        // isclose as ATen defines it: equal (which is what makes equal
+        // infinities tie), or a FINITE difference within the threshold
+        // (thr is +inf at an infinite best, where |q - best| is too)
+        const float q = qbuf[i];
+        const float d = fabsf(q - best);
+        if (q == best || (d <= thr && d < INFINITY)) {
             ++cnt;
             // unordered slots, each packing (position, q value) so the
             // host tie-break needs NO second device fetch; the host
@@ -1049,8 +1065,9 @@ acq_select_ties_kernel(const float* __restrict__ qbuf,
                 reinterpret_cast<unsigned long long*>(tbuf), 1ull);
             if (slot < cap)
                 tbuf[1 + slot] = ((long long)i << 32)
-                    | (unsigned int)__float_as_int(qbuf[i]);
+                    | (unsigned int)__float_as_int(q);
         }
+    }
     __shared__ int sc[BLOCK];
     sc[threadIdx.x] = cnt;
     __syncthreads();

@@ -600,9 +600,10 @@ class CODA(ModelSelector):
         # fused epilogue: qbuf = active ? H0 + q0 : -inf; out =
         # [masked max, first argmax, isclose tie count].  Replaces the
         # ~10-launch torch chain (where/max/isclose/sum/copies,
-        # ~120 us/step at B=50k); identical semantics - when the tie
-        # count is 1 the argmax is unique, and ties go through the
-        # seeded host random.choice either way (_acq_result).
+        # ~120 us/step at B=50k); torch.isclose on finite and infinite
+        # values, NaN skipped (tests/acq_ref.py is the contract) - when
+        # the tie count is 1 the argmax is unique, and ties go through
+        # the seeded host random.choice either way (_acq_result).
         ops._ext.acq_select(q0.contiguous(), H0.reshape(1).contiguous(),
                             acq.active, acq.qbuf, acq.out, acq.ties)
 
