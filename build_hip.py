@@ -15,14 +15,13 @@ import sys
 import sysconfig
 
 REPO = os.path.dirname(os.path.abspath(__file__))
-SRC = [os.path.join(REPO, "coda_amd", "ops", "hip", "pbest.hip"),
-       os.path.join(REPO, "coda_amd", "ops", "hip", "pair.hip"),
-       os.path.join(REPO, "coda_amd", "ops", "hip", "ingest.hip"),
-       os.path.join(REPO, "coda_amd", "ops", "hip", "ingest_f16.hip"),
-       os.path.join(REPO, "coda_amd", "ops", "hip", "ingest_logits.hip"),
-       os.path.join(REPO, "coda_amd", "ops", "hip", "modelpicker.hip")]
+HIP_DIR = os.path.join(REPO, "coda_amd", "ops", "hip")
+SRC = [os.path.join(HIP_DIR, f) for f in (
+    "module.hip", "pbest.hip", "table.hip", "label.hip", "pair.hip",
+    "ingest.hip", "ingest_f16.hip", "ingest_logits.hip", "modelpicker.hip")]
 # headers the sources include: part of the up-to-date check only
-HDR = [os.path.join(REPO, "coda_amd", "ops", "hip", "ingest_kernel.h")]
+HDR = [os.path.join(HIP_DIR, f) for f in (
+    "wave.h", "beta_grid.h", "host_util.h", "ingest_kernel.h")]
 OUT = os.path.join(REPO, "coda_amd", "ops",
                    "_coda_hip.cpython-310-x86_64-linux-gnu.so")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
@@ -46,12 +45,12 @@ def build(force: bool = False, verbose: bool = True) -> str:
     libdirs = ce.library_paths()
     abi = int(torch.compiled_with_cxx11_abi())
 
-    # Tuned on MI355X (scripts/kernel_bench.py sweep): DPP wave scan +
-    # 4-waves/SIMD launch bound = 1.86x the untuned kernel (82.9 -> 44.6
-    # ns/row on the fused EIG kernel at H=128, C=1000).
+    # No tuning flags: the DPP wave scan (wave.h) and the 4-waves/SIMD
+    # launch bound (beta_grid.h) that the MI355X sweep chose are written
+    # into the sources (sweep record: profiles/README.md). One hipcc call;
+    # the sources find their headers next to themselves.
     cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17",
            "-fPIC", "-shared", *SRC, "-o", OUT,
-           "-DCODA_DPP_SCAN=1", "-DCODA_MIN_WAVES=4",
            "-DTORCH_EXTENSION_NAME=_coda_hip",
            "-DTORCH_API_INCLUDE_EXTENSION_H",
            f"-D_GLIBCXX_USE_CXX11_ABI={abi}",

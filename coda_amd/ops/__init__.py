@@ -187,7 +187,7 @@ def mixture_entropy(pbest_rows: torch.Tensor, pi_hat: torch.Tensor):
 
     GPU: torch reduces the (C, H) column sum with a 32-thread launch
     (~22 us at C=1000, H=128); the HIP twin (mix_part/mix_combine in
-    pbest.hip) does slab partials + a fused entropy contraction in
+    label.hip) does slab partials + a fused entropy contraction in
     ~8 us, deterministic fixed-order sums."""
     H = pbest_rows.size(1)
     if (pbest_rows.is_cuda and H % 4 == 0 and H <= 1024

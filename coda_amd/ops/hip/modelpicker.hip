@@ -36,7 +36,7 @@
 //   1. each lane folds its positions into (seen-a-mark, sums since the
 //      last mark);
 //   2. a segmented inclusive scan on the DPP row_shr/row_bcast ladder
-//      (the ladder of pbest.hip, with the segmented operator) hands each
+//      (the ladder of wave.h, with the segmented operator) hands each
 //      lane the open segment's sums from the lanes before it;
 //   3. each lane walks its positions again, closing a segment - one
 //      closed-form evaluation - at every mark; the lane that owns
@@ -51,6 +51,7 @@
 #include <torch/extension.h>
 #include <hip/hip_runtime.h>
 #include <c10/hip/HIPStream.h>
+#include "wave.h"  // dpp_mov, wave_reduce_sum
 
 namespace mpops {
 
@@ -60,27 +61,6 @@ constexpr int kMaxH = 1024;
 constexpr int kMaxR = kMaxH / 64;
 constexpr int kMaxBlocks = 2048;   // 8 blocks of 4 waves per CU
 constexpr float kInvLn2 = 1.4426950408889634f;
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp_mov(int x) {
-    // moved-in value; 0 where the lane has no source or its row is masked
-    return __builtin_amdgcn_update_dpp(0, x, CTRL, ROW_MASK, 0xf, true);
-}
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_add(float x) {
-    return x + __int_as_float(dpp_mov<CTRL, ROW_MASK>(__float_as_int(x)));
-}
-
-__device__ __forceinline__ float wave_reduce(float v) {
-    v = dpp_add<0x111, 0xf>(v);  // row_shr:1
-    v = dpp_add<0x112, 0xf>(v);  // row_shr:2
-    v = dpp_add<0x114, 0xf>(v);  // row_shr:4
-    v = dpp_add<0x118, 0xf>(v);  // row_shr:8
-    v = dpp_add<0x142, 0xa>(v);  // row_bcast:15
-    v = dpp_add<0x143, 0xc>(v);  // row_bcast:31
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
 
 // One ladder step of the segmented scan: (f, s, t) <- moved (+) own with
 // (f1, v1) (+) (f2, v2) = (f1 | f2, f2 ? v2 : v1 + v2). A lane without a
@@ -243,7 +223,7 @@ modelpicker_dev_kernel(const unsigned short* __restrict__ packed,  // (N, H)
             // the last segment; a row without any mark is one class on
             // all models and contributes exactly 0
             if (lane == last_lane && cf) acc += closed_form(rs, rt, k);
-            const float total = wave_reduce(acc);
+            const float total = wave_reduce_sum(acc);
             if (lane == 0) dev[n] = total;
         }
         act = act_nxt;

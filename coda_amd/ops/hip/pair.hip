@@ -53,6 +53,7 @@
 #include <hip/hip_runtime.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_bfloat16.h>
+#include "wave.h"  // wave_reduce_sum, row16_reduce
 
 #define P_POINTS 256
 #define BLOCK 256
@@ -62,36 +63,6 @@ namespace pairops {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 half4v __attribute__((ext_vector_type(4)));
-
-#ifdef CODA_DPP_SCAN
-// Wave64 sum via the GCN DPP row_shr/row_bcast ladder: 6 VALU ops at
-// 1-2 cycle dependent latency each, vs ~7 dependent ds_bpermute rounds
-// (~30+ cycles each) for the __shfl ladder. Same ladder as pbest.hip.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_add(float x) {
-    int moved = __builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL,
-                                            ROW_MASK, 0xf, true);
-    return x + __int_as_float(moved);
-}
-
-__device__ __forceinline__ float wave_reduce(float v) {
-    v = dpp_add<0x111, 0xf>(v);  // row_shr:1
-    v = dpp_add<0x112, 0xf>(v);  // row_shr:2
-    v = dpp_add<0x114, 0xf>(v);  // row_shr:4
-    v = dpp_add<0x118, 0xf>(v);  // row_shr:8
-    v = dpp_add<0x142, 0xa>(v);  // row_bcast:15
-    v = dpp_add<0x143, 0xc>(v);  // row_bcast:31
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v),
-                                                    63));
-}
-#else
-__device__ __forceinline__ float wave_reduce(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v += __shfl_down(v, off, 64);
-    return __shfl(v, 0, 64);
-}
-#endif
 
 // ---------------------------------------------------------------------
 // A-operand build: a16[k, p] = 2^(sum_{h in seg(k)} delta16[c_k, h, p])
@@ -295,7 +266,7 @@ pair_gemm_entropy16_kernel(const hip_bfloat16* __restrict__ a16,
             const int v = (vm[h >> 5] >> (h & 31)) & 1;
             tot += mrow[2 * h + v];
         }
-        tot = wave_reduce(tot);
+        tot = wave_reduce_sum(tot);
         const float inv = 1.0f / fmaxf(tot, 1e-30f);
         const float pic = pi_hat[c];
         float ent = 0.f;
@@ -307,7 +278,7 @@ pair_gemm_entropy16_kernel(const hip_bfloat16* __restrict__ a16,
                 1e-12f);
             ent += -mm * __log2f(mm);
         }
-        ent = wave_reduce(ent);
+        ent = wave_reduce_sum(ent);
         if (lane == 0) h_after[k] = ent;
     }
 }
@@ -329,22 +300,6 @@ pair_gemm_entropy16_kernel(const hip_bfloat16* __restrict__ a16,
                      // put odd-row b128 reads at =4 mod 8 words: +60
                      // stall cycles each on CDNA4)
 #define BLOCK2 512
-
-__device__ __forceinline__ float row16_reduce(float v) {
-#ifdef CODA_DPP_SCAN
-    v = dpp_add<0x111, 0xf>(v);  // row_shr:1
-    v = dpp_add<0x112, 0xf>(v);  // row_shr:2
-    v = dpp_add<0x114, 0xf>(v);  // row_shr:4
-    v = dpp_add<0x118, 0xf>(v);  // row_shr:8 -> lane15 of each row
-#else
-#pragma unroll
-    for (int off = 1; off < 16; off <<= 1) {
-        float n = __shfl_up(v, off, 16);
-        if ((threadIdx.x & 15) >= off) v += n;
-    }
-#endif
-    return __shfl(v, 15, 16);    // broadcast row total to all 16 lanes
-}
 
 // One selected column's entropy term, added to the lane's running sum:
 // pb = m * inv (the pair's normalized P(best) for model h), mm =
@@ -834,7 +789,7 @@ pair_entropy_wide_kernel(const hip_bfloat16* __restrict__ m,  // (K, 2H)
         val[i] = (float)mrow[2 * h + v];
         tot += val[i];
     }
-    tot = wave_reduce(tot);
+    tot = wave_reduce_sum(tot);
     const float inv = 1.0f / fmaxf(tot, 1e-30f);
     const float pic = pi_hat[c];
     float ent = 0.f;
@@ -846,7 +801,7 @@ pair_entropy_wide_kernel(const hip_bfloat16* __restrict__ m,  // (K, 2H)
             1e-12f);
         ent += -mm * __log2f(mm);
     }
-    ent = wave_reduce(ent);
+    ent = wave_reduce_sum(ent);
     if (lane == 0) h_after[k] = ent;
 }
 
@@ -894,7 +849,7 @@ pair_eig_finalize_kernel(const float* __restrict__ h_after,   // (K,)
         corr += arow[c2] * (h_after[k] - h_base[c2]);
     }
     (void)pair_c;
-    const float tot = wave_reduce(base + corr);
+    const float tot = wave_reduce_sum(base + corr);
     if (lane == 0) q[b] = H_before - tot * inv;
 }
 
@@ -925,7 +880,7 @@ pair_entropy_wide_cls_kernel(const hip_bfloat16* __restrict__ m,  // (K, 2H)
         const int v = (b >= 0 && cls[(size_t)b * H + h] == c) ? 1 : 0;
         tot += (float)mrow[2 * h + v];
     }
-    tot = wave_reduce(tot);
+    tot = wave_reduce_sum(tot);
     const float inv = 1.0f / fmaxf(tot, 1e-30f);
     const float pic = pi_hat[c];
     float ent = 0.f;
@@ -937,7 +892,7 @@ pair_entropy_wide_cls_kernel(const hip_bfloat16* __restrict__ m,  // (K, 2H)
             1e-12f);
         ent += -mm * __log2f(mm);
     }
-    ent = wave_reduce(ent);
+    ent = wave_reduce_sum(ent);
     if (lane == 0) h_after[k] = ent;
 }
 

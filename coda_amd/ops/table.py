@@ -191,7 +191,7 @@ def eig_chunk_table(tables: EigTables, chunk_classes: torch.Tensor,
     """(B,) EIG for a candidate chunk through the v2 tables.
 
     GPU path: the es_build / eig_assemble_k fusion kernels around the
-    batched GEMM (see pbest.hip); CPU path: the torch composition above.
+    batched GEMM (see table.hip); CPU path: the torch composition above.
     """
     EG, delta, s_base, w = tables.EG, tables.delta, tables.s_base, tables.weights
     C, H, _, P = EG.shape
@@ -292,7 +292,7 @@ def table_commit_row(tables: EigTables, dirichlets: torch.Tensor,
     if (t.eg16 is not None and t.egw is not None
             and t.delta16 is not None and t.dall is not None
             and O.hip_available()):
-        # one fused commit (trc_* kernels in pbest.hip): the torch chain
+        # one fused commit (trc_* kernels in table.hip): the torch chain
         # below was ~14 in-graph launches incl. two 32-thread strided
         # reductions (10-24 us each)
         return O._ext.table_commit_row(

@@ -1,7 +1,7 @@
 // Standalone variant sweep for the pi_marginal kernel (the scaled
 // column-sum pi = (1/rowsum) @ adjusted, (N,C) fp32 -> (C,)).
 //
-// Shipping kernel (ops/hip/pbest.hip pi_marginal_kernel) measures
+// Shipping kernel (ops/hip/label.hip pi_marginal_kernel) measures
 // 173 us at N=50k, C=1000 vs a ~25 us streaming floor; suspects are
 // (a) only 4 float4 loads in flight per lane and (b) 1.5M atomicAdds
 // onto 1000 float addresses. This probe times the current schedule

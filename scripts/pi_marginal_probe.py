@@ -3,7 +3,7 @@
 Compiles scripts/pi_marginal_probe.hip on the box, checks every variant
 against the torch fp32 reference, and times them at the headline shape
 (N=50k, C=1000) plus the wide-pool shape. Prints one line per variant;
-port only an evidenced winner into ops/hip/pbest.hip.
+port only an evidenced winner into ops/hip/label.hip.
 """
 import os
 import sys

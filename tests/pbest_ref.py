@@ -1,12 +1,12 @@
 """fp64 stage references for the v1 P(best) / EIG kernels (not itself a
 test).
 
-Each function is the CONTRACT of one stage of the oldest kernel family
-in coda_amd/ops/hip/pbest.hip (pbest_kernel, pbest_row_kernel, the
+Each function is the CONTRACT of one stage of the oldest kernel family,
+coda_amd/ops/hip/pbest.hip (pbest_kernel, pbest_row_kernel, the
 phase-1 / phase-2 kernels and their wide twins, eig_hyp_kernel and the
 EIG phase kernels), written in plain torch on CPU tensors and evaluated
 in fp64 on exactly the fp32 operands the kernel receives. The curve
-math (LaneGrid::pdf4 / cdf4) is tests/table_ref.curves, shared with the
+math (LaneGrid::pdf4 / cdf4, beta_grid.h) is tests/table_ref.curves, shared with the
 v2 table references; the entropy epilogue is tests/pair_ref.ref_entropy.
 
 `f32=True` re-runs the same reference with every operation rounded to
@@ -36,7 +36,7 @@ from tests import table_ref as TR
 from tests.pair_ref import _f32c, _r32, _same
 
 P = TR.P
-ROWS_PER_BLOCK = 4                # pbest.hip: waves (rows) per workgroup
+ROWS_PER_BLOCK = 4                # beta_grid.h: waves (rows) per workgroup
 # the kernel's float literals at their fp32 values
 LOG2_CLAMP = float(torch.tensor(115.41560327111707, dtype=torch.float32))
 EPS = _f32c(1e-30, torch.float64)

@@ -1,7 +1,7 @@
 """fp64 stage references for the v2 table engine (not itself a test).
 
 Each function is the CONTRACT of one kernel of the table path in
-coda_amd/ops/hip/pbest.hip (es_build*, eig_assemble_k, eig_totals,
+coda_amd/ops/hip/table.hip (es_build*, eig_assemble_k, eig_totals,
 eig_entropy, beta_row_tables, table_commit_*), written in plain torch on
 CPU tensors and evaluated in fp64 on exactly the tensors the kernel
 receives: the fp32 tables, the fp32 dall and a bf16 M are INPUTS, so
@@ -28,7 +28,7 @@ from tests import pair_ref as PR
 from tests.pair_ref import _f32c, _r32, _same, _sum32
 
 P = 256
-ES_LONG_ROW = 512                 # pbest.hip: rows above go block-per-row
+ES_LONG_ROW = 512                 # table.hip: rows above go block-per-row
 LOG2E = 1.4426950408889634
 # branch codes of an es_build row: bit 0 = complement, bit 1 = long
 DIRECT_SHORT, COMP_SHORT, DIRECT_LONG, COMP_LONG = 0, 1, 2, 3

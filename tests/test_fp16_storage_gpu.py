@@ -1,6 +1,6 @@
 """GPU tests of fp16 prediction-pool storage: the fp16-storage ingest kernels
 (coda_amd/ops/hip/ingest_f16.hip), the fp16 pi_hat_delta kernels
-(pbest.hip) and CODA end to end.
+(label.hip) and CODA end to end.
 
 Nothing here is approximate. The ingest contract is bit-level (stored bits
 == torch's CPU `wire.float().to(torch.float16)`, lowest-index argmax and an

@@ -1,9 +1,10 @@
-"""Kernel resource audit: compile the HIP source with
--Rpass-analysis=kernel-resource-usage and bound register/LDS/spill use.
+"""Kernel resource audit: compile the engine sources (pbest.hip, table.hip,
+label.hip) with -Rpass-analysis=kernel-resource-usage and bound
+register/LDS/spill use.
 
 Catches silent codegen regressions (occupancy cliffs, new scratch spills)
 without a GPU - hipcc cross-compiles gfx950 anywhere. Loose bounds: the
-tuned CODA_LB kernels intentionally spill ~50 VGPRs for 4 waves/SIMD
+tuned v1 kernels intentionally spill ~50 VGPRs for 4 waves/SIMD
 (measured faster - profiles/README.md); the glue kernels must not spill
 at all.
 """
@@ -25,23 +26,31 @@ def resource_report(tmp_path_factory):
     import torch.utils.cpp_extension as ce
     import sysconfig
     import torch
-    out = tmp_path_factory.mktemp("kra") / "pbest.o"
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
-           "-c", os.path.join(REPO, "coda_amd", "ops", "hip", "pbest.hip"),
-           "-o", str(out), "-Rpass-analysis=kernel-resource-usage",
-           "-DCODA_DPP_SCAN=1", "-DCODA_MIN_WAVES=4",
-           "-DTORCH_EXTENSION_NAME=_kra", "-DTORCH_API_INCLUDE_EXTENSION_H",
-           f"-D_GLIBCXX_USE_CXX11_ABI={int(torch.compiled_with_cxx11_abi())}",
-           "-DUSE_ROCM=1", "-D__HIP_PLATFORM_AMD__=1"]
-    cmd += [f"-I{p}" for p in ce.include_paths()]
-    cmd += [f"-I{sysconfig.get_paths()['include']}"]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
+    tmp = tmp_path_factory.mktemp("kra")
+    hip = os.path.join(REPO, "coda_amd", "ops", "hip")
+    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
+             "-Rpass-analysis=kernel-resource-usage",
+             "-DTORCH_EXTENSION_NAME=_kra", "-DTORCH_API_INCLUDE_EXTENSION_H",
+             f"-D_GLIBCXX_USE_CXX11_ABI={int(torch.compiled_with_cxx11_abi())}",
+             "-DUSE_ROCM=1", "-D__HIP_PLATFORM_AMD__=1", f"-I{hip}"]
+    flags += [f"-I{p}" for p in ce.include_paths()]
+    flags += [f"-I{sysconfig.get_paths()['include']}"]
+    # the three engine sources, compiled side by side; remarks merged
+    procs = [subprocess.Popen(
+        [HIPCC, *flags, "-c", os.path.join(hip, f"{name}.hip"),
+         "-o", str(tmp / f"{name}.o")],
+        stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
+        for name in ("pbest", "table", "label")]
+    remarks = []
+    for p in procs:
+        err = p.communicate(timeout=600)[1]
+        assert p.returncode == 0, err[-3000:]
+        remarks += err.splitlines()
     # parse blocks: "remark: <kernel> ... SGPRs: n ... VGPRs: n ...
     # ScratchSize [bytes/lane]: n ... Occupancy [waves/SIMD]: n"
     kernels = {}
     cur = None
-    for line in r.stderr.splitlines():
+    for line in remarks:
         m = re.search(r"Function Name:\s*(\S+)", line)
         if m:
             cur = m.group(1)
@@ -54,7 +63,7 @@ def resource_report(tmp_path_factory):
             m = re.search(pat, line)
             if m and cur:
                 kernels[cur][key] = int(m.group(1))
-    assert kernels, "no resource remarks parsed:\n" + r.stderr[:2000]
+    assert kernels, "no resource remarks parsed:\n" + "\n".join(remarks[:40])
     return kernels
 
 

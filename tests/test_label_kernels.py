@@ -1,4 +1,5 @@
-"""fp64 tests of the label-update HIP kernels (GPU): pi_hat_delta and
+"""fp64 tests of the label-update HIP kernels (GPU,
+coda_amd/ops/hip/label.hip): pi_hat_delta and
 its two H-windowed variants, pi_marginal (both routes), mixture_entropy,
 col_add and dirichlet_add, each called on its own with CPU-built
 inputs. They run inside the captured label-update graph on every label.

@@ -330,7 +330,6 @@ def test_cache_kernels_resource_envelope(tmp_path):
            "-c", os.path.join(REPO, "coda_amd", "ops", "hip", "pair.hip"),
            "-o", str(tmp_path / "pair.o"),
            "-Rpass-analysis=kernel-resource-usage",
-           "-DCODA_DPP_SCAN=1", "-DCODA_MIN_WAVES=4",
            "-DTORCH_EXTENSION_NAME=_kra", "-DTORCH_API_INCLUDE_EXTENSION_H",
            f"-D_GLIBCXX_USE_CXX11_ABI={int(torch.compiled_with_cxx11_abi())}",
            "-DUSE_ROCM=1", "-D__HIP_PLATFORM_AMD__=1"]

@@ -1,6 +1,6 @@
 """Stage-level fp64 tests of the v1 P(best) / EIG HIP kernels (GPU).
 
-Every kernel of the oldest family in coda_amd/ops/hip/pbest.hip
+Every kernel of the oldest family, coda_amd/ops/hip/pbest.hip
 (pbest_kernel, pbest_row_kernel, pbest_phase1 / pbest_phase2 and their
 wide twins, eig_phase1 / eig_phase2, eig_hyp_kernel) is driven on its
 own through the `ops._ext` bindings and compared with the fp64

@@ -1,6 +1,6 @@
 """Stage-level fp64 tests of the table engine's HIP kernels (GPU).
 
-Every v2 kernel of coda_amd/ops/hip/pbest.hip (es_build with its
+Every v2 kernel of coda_amd/ops/hip/table.hip (es_build with its
 block-per-row companion, es_build_gathered, eig_assemble_k, eig_totals,
 eig_entropy, beta_row_tables, table_commit_row / table_commit_cols) is
 driven on its own through the `ops._ext` bindings and compared with the
