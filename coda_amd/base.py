@@ -13,9 +13,14 @@ class ModelSelector:
     Attributes:
         stochastic: True if the algorithm made any random choice so far, in
             which case the harness runs additional seeds.
+        supports_batch: True if the algorithm hands out a batch of points
+            per acquisition (get_next_items_to_label / add_labels); the
+            harness labels the others one point at a time.
     """
 
     stochastic: bool = False
+    # True where get_next_items_to_label(k) / add_labels exist
+    supports_batch: bool = False
 
     def get_next_item_to_label(self):
         """Pick the next unlabeled point to send to the oracle.

@@ -31,6 +31,7 @@ from .reference import (  # re-export cheap ops + constants
     accuracy_losses, entropy_acquisition, vma_pairwise, lure_weights,
     MODELPICKER_MAX_H, MODELPICKER_MAX_C, ModelPickerStruct,
     modelpicker_build, modelpicker_prologue,
+    ACQ_TOPK_MAX, acq_topk, group_rows,
 )
 
 _ext = None

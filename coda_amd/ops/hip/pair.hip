@@ -49,6 +49,8 @@
 // contiguous bytes per lane. Layout verified by the mfma_probe test
 // (tests/test_gpu.py).
 
+#include <climits>
+#include <initializer_list>
 #include <torch/extension.h>
 #include <hip/hip_runtime.h>
 #include <c10/hip/HIPStream.h>
@@ -1034,6 +1036,248 @@ acq_select_ties_kernel(const float* __restrict__ qbuf,
         atomicAdd(out + 2, (double)sc[0]);
 }
 
+// ---------------------------------------------------------------------
+// Batch acquisition: the K best DISTINCT candidates of the qbuf the
+// epilogue above left, in rank order (q descending, position ascending,
+// -0 as +0), optionally one per group. The contract, as plain numpy, is
+// tests/acq_topk_ref.py.
+//
+// Every active candidate maps to one u64 key, high word the monotone
+// unsigned image of its q, low word 0xFFFFFFFF - position; 0 is "empty".
+// The order is then "larger key first" and keys are unique, so every
+// reduction is an integer max or an integer count: order-independent,
+// bit-reproducible through atomics.
+//   prep     zero the digit histograms, the slot counter and (groups)
+//            the best-per-group keys
+//   group    (groups only) u64 atomicMax of each candidate's key into
+//            its group's word: the survivors are the group winners
+//   hist x6  radix select of the K-th largest key, most significant
+//            digit first (11 bits a pass, 9 in the last). Each block
+//            derives the prefix found so far from the previous pass's
+//            histogram, counts its slice's matching keys per digit in
+//            LDS and adds the counts to the pass's global histogram
+//   gather   keys >= the K-th largest go to unordered slots
+//   sort     one block: bitonic sort of the <= 1024 slots, decoded to
+//            (position << 32) | q bits, padded with -1
+// A kernel boundary is the only ordering between blocks.
+// ---------------------------------------------------------------------
+#define TOPK_MAX 1024
+#define TOPK_BINS 2048
+#define TOPK_PASSES 6
+// int32 workspace: [0, PASSES*BINS) histograms, then the slot counter,
+// then (prefix lo, prefix hi, still wanted, take-all) per pass
+#define TOPK_WS_CNT (TOPK_PASSES * TOPK_BINS)
+#define TOPK_WS_STATE (TOPK_WS_CNT + 4)
+#define TOPK_WS_INTS (TOPK_WS_STATE + 4 * TOPK_PASSES)
+
+__device__ __forceinline__ int topk_shift(int p) {
+    return p == TOPK_PASSES - 1 ? 0 : 64 - 11 * (p + 1);
+}
+
+__device__ __forceinline__ int topk_mask(int p) {
+    return p == TOPK_PASSES - 1 ? 511 : TOPK_BINS - 1;
+}
+
+__device__ __forceinline__ unsigned long long
+topk_key_of(float q, int i) {
+    if (q == 0.0f) q = 0.0f;                    // -0 orders as +0
+    const unsigned int u = (unsigned int)__float_as_int(q);
+    const unsigned int m = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((unsigned long long)m << 32) | (0xFFFFFFFFu - (unsigned int)i);
+}
+
+// survivor i's key: the group winners when keys is given, else built
+// from the masked q
+__device__ __forceinline__ unsigned long long
+topk_load(const unsigned long long* __restrict__ keys,
+          const float* __restrict__ qbuf, const bool* __restrict__ active,
+          int i) {
+    if (keys != nullptr) return keys[i];
+    return active[i] ? topk_key_of(qbuf[i], i) : 0ull;
+}
+
+struct TopkState {
+    unsigned long long prefix;  // digits found so far, in place
+    int want;                   // ranks still to find under the prefix
+    int all;                    // fewer survivors than K: take them all
+};
+
+// State entering pass p, by every thread of a BLOCK-thread block: the
+// state entering pass p-1 (written by that pass's block 0) advanced by
+// that pass's finished histogram. Pass 0 starts from (0, K).
+__device__ TopkState topk_state(const int* __restrict__ ws, int p, int K) {
+    __shared__ int ssum[BLOCK];
+    __shared__ int sres[2];     // digit, ranks wanted inside it
+    TopkState s;
+    if (p == 0) {
+        s.prefix = 0ull; s.want = K; s.all = 0;
+        return s;
+    }
+    if (p == 1) {
+        s.prefix = 0ull; s.want = K; s.all = 0;
+    } else {
+        const int* st = ws + TOPK_WS_STATE + 4 * (p - 1);
+        s.prefix = ((unsigned long long)(unsigned int)st[1] << 32)
+            | (unsigned int)st[0];
+        s.want = st[2];
+        s.all = st[3];
+    }
+    if (s.all) return s;        // uniform: read from global
+    const int* h = ws + (p - 1) * TOPK_BINS + threadIdx.x * 8;
+    int hv[8];
+    int tot = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { hv[j] = h[j]; tot += hv[j]; }
+    ssum[threadIdx.x] = tot;
+    if (threadIdx.x == 0) sres[0] = -1;
+    __syncthreads();
+    // inclusive suffix sums over the threads' totals
+    for (int d = 1; d < BLOCK; d <<= 1) {
+        const int add = threadIdx.x + d < BLOCK
+            ? ssum[threadIdx.x + d] : 0;
+        __syncthreads();
+        ssum[threadIdx.x] += add;
+        __syncthreads();
+    }
+    int above = ssum[threadIdx.x] - tot;   // counts in higher digits
+    if (above < s.want && s.want <= above + tot) {
+#pragma unroll
+        for (int j = 7; j >= 0; --j) {
+            if (above < s.want && s.want <= above + hv[j]) {
+                sres[0] = threadIdx.x * 8 + j;
+                sres[1] = s.want - above;
+            }
+            above += hv[j];
+        }
+    }
+    __syncthreads();
+    const int digit = sres[0];
+    const int want = sres[1];
+    __syncthreads();            // sres is reused by the caller's next call
+    if (digit < 0) {
+        s.all = 1;
+    } else {
+        s.prefix |= (unsigned long long)digit << topk_shift(p - 1);
+        s.want = want;
+    }
+    return s;
+}
+
+__global__ void __launch_bounds__(BLOCK)
+topk_prep_kernel(int* __restrict__ ws,
+                 unsigned long long* __restrict__ gbest, int G) {
+    const int t = blockIdx.x * BLOCK + threadIdx.x;
+    const int n = gridDim.x * BLOCK;
+    for (int i = t; i <= TOPK_WS_CNT; i += n) ws[i] = 0;
+    for (int i = t; i < G; i += n) gbest[i] = 0ull;
+}
+
+__global__ void __launch_bounds__(BLOCK)
+topk_group_kernel(const float* __restrict__ qbuf,
+                  const bool* __restrict__ active,
+                  const int* __restrict__ group_of,
+                  unsigned long long* __restrict__ gbest, int G, int B) {
+    const int per = (B + gridDim.x - 1) / gridDim.x;
+    const int b0 = blockIdx.x * per;
+    const int b1 = min(b0 + per, B);
+    for (int i = b0 + threadIdx.x; i < b1; i += BLOCK) {
+        if (!active[i]) continue;
+        const int g = group_of[i];
+        if ((unsigned int)g < (unsigned int)G)
+            atomicMax(gbest + g, topk_key_of(qbuf[i], i));
+    }
+}
+
+__global__ void __launch_bounds__(BLOCK)
+topk_hist_kernel(const unsigned long long* __restrict__ keys,
+                 const float* __restrict__ qbuf,
+                 const bool* __restrict__ active,
+                 int* __restrict__ ws, int p, int K, int n) {
+    __shared__ int hist[TOPK_BINS];
+    for (int j = threadIdx.x; j < TOPK_BINS; j += BLOCK) hist[j] = 0;
+    const TopkState s = topk_state(ws, p, K);   // syncs (p > 0)
+    if (p > 0 && blockIdx.x == 0 && threadIdx.x == 0) {
+        int* st = ws + TOPK_WS_STATE + 4 * p;
+        st[0] = (int)(unsigned int)s.prefix;
+        st[1] = (int)(unsigned int)(s.prefix >> 32);
+        st[2] = s.want;
+        st[3] = s.all;
+    }
+    if (s.all) return;
+    __syncthreads();
+    const int shift = topk_shift(p);
+    const int above = p == 0 ? 64 : topk_shift(p - 1);
+    const int per = (n + gridDim.x - 1) / gridDim.x;
+    const int b0 = blockIdx.x * per;
+    const int b1 = min(b0 + per, n);
+    for (int i = b0 + threadIdx.x; i < b1; i += BLOCK) {
+        const unsigned long long k = topk_load(keys, qbuf, active, i);
+        if (k == 0ull) continue;
+        if (above < 64 && (k >> above) != (s.prefix >> above)) continue;
+        atomicAdd(&hist[(int)(k >> shift) & topk_mask(p)], 1);
+    }
+    __syncthreads();
+    int* gh = ws + p * TOPK_BINS;
+    for (int j = threadIdx.x; j < TOPK_BINS; j += BLOCK)
+        if (hist[j] != 0) atomicAdd(gh + j, hist[j]);
+}
+
+__global__ void __launch_bounds__(BLOCK)
+topk_gather_kernel(const unsigned long long* __restrict__ keys,
+                   const float* __restrict__ qbuf,
+                   const bool* __restrict__ active,
+                   int* __restrict__ ws,
+                   unsigned long long* __restrict__ sel, int K, int n) {
+    const TopkState s = topk_state(ws, TOPK_PASSES, K);
+    const unsigned long long thr = s.all ? 1ull : s.prefix;
+    const int per = (n + gridDim.x - 1) / gridDim.x;
+    const int b0 = blockIdx.x * per;
+    const int b1 = min(b0 + per, n);
+    for (int i = b0 + threadIdx.x; i < b1; i += BLOCK) {
+        const unsigned long long k = topk_load(keys, qbuf, active, i);
+        if (k == 0ull || k < thr) continue;
+        const int slot = atomicAdd(ws + TOPK_WS_CNT, 1);
+        if (slot < TOPK_MAX) sel[slot] = k;
+    }
+}
+
+__global__ void __launch_bounds__(TOPK_MAX)
+topk_sort_kernel(const unsigned long long* __restrict__ sel,
+                 const int* __restrict__ ws,
+                 const float* __restrict__ qbuf,
+                 long long* __restrict__ topk, int K) {
+    __shared__ unsigned long long sk[TOPK_MAX];
+    const int t = threadIdx.x;
+    const int cnt = min(ws[TOPK_WS_CNT], TOPK_MAX);
+    sk[t] = t < cnt ? sel[t] : 0ull;
+    __syncthreads();
+    for (int k = 2; k <= TOPK_MAX; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            const int o = t ^ j;
+            if (o > t) {
+                const unsigned long long a = sk[t], b = sk[o];
+                // descending overall
+                if (((t & k) == 0) ? (a < b) : (a > b)) {
+                    sk[t] = b;
+                    sk[o] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (t < K) {
+        const unsigned long long k = sk[t];
+        long long w = -1;
+        if (k != 0ull && t < cnt) {
+            const unsigned int pos = 0xFFFFFFFFu - (unsigned int)k;
+            // the entry's own bits (a -0 stays -0), as the tie words
+            w = ((long long)pos << 32)
+                | (unsigned int)__float_as_int(qbuf[pos]);
+        }
+        topk[t] = w;
+    }
+}
+
 // MFMA layout probe (correctness insurance, not a production op):
 // C (16,16) = A (16,32) x B stored row-major as BT (16 cols x 32 k).
 __global__ void mfma_probe_kernel(const float* __restrict__ a,   // (16,32)
@@ -1372,7 +1616,10 @@ torch::Tensor pair_eig_finalize(torch::Tensor h_after,
 
 void acq_select(torch::Tensor q0, torch::Tensor h0, torch::Tensor active,
                 torch::Tensor qbuf, torch::Tensor out,
-                torch::Tensor ties) {
+                torch::Tensor ties,
+                c10::optional<torch::Tensor> topk_o,
+                c10::optional<torch::Tensor> group_of_o,
+                int64_t n_groups) {
     TORCH_CHECK(q0.is_cuda() && q0.dtype() == torch::kFloat32
                 && q0.is_contiguous(), "q0 must be contiguous fp32");
     TORCH_CHECK(h0.dtype() == torch::kFloat32 && h0.numel() == 1);
@@ -1386,6 +1633,36 @@ void acq_select(torch::Tensor q0, torch::Tensor h0, torch::Tensor active,
                 && ties.numel() >= 2, "ties buffer too small");
     const int cap = ties.numel() - 1;
     const int B = q0.numel();
+    // batch outputs: everything is checked before the first launch
+    const bool want_topk = topk_o.has_value() && topk_o->defined();
+    const bool grouped = group_of_o.has_value() && group_of_o->defined();
+    TORCH_CHECK(want_topk || !grouped, "group_of needs a topk buffer");
+    int K = 0, G = 0;
+    if (want_topk) {
+        const auto& topk = *topk_o;
+        TORCH_CHECK(B >= 1, "topk needs at least one candidate");
+        TORCH_CHECK(topk.dtype() == torch::kInt64 && topk.is_contiguous()
+                    && topk.dim() == 1, "topk must be contiguous int64");
+        TORCH_CHECK(topk.numel() >= 1 && topk.numel() <= TOPK_MAX,
+                    "topk holds 1 to ", TOPK_MAX, " slots");
+        K = topk.numel();
+        for (const torch::Tensor* t : std::initializer_list<
+                 const torch::Tensor*>{&h0, &active, &qbuf, &out, &ties,
+                                       &topk})
+            TORCH_CHECK(t->device() == q0.device(),
+                        "every acq_select tensor lives on q0's device");
+        if (grouped) {
+            const auto& gof = *group_of_o;
+            TORCH_CHECK(gof.dtype() == torch::kInt32 && gof.is_contiguous()
+                        && gof.numel() == B,
+                        "group_of must be contiguous int32 (B,)");
+            TORCH_CHECK(gof.device() == q0.device(),
+                        "every acq_select tensor lives on q0's device");
+            TORCH_CHECK(n_groups >= 1 && n_groups <= INT_MAX,
+                        "n_groups must be at least 1 with group_of");
+            G = (int)n_groups;
+        }
+    }
     auto pmax = torch::empty({ACQ_GRID}, q0.options());
     auto pidx = torch::empty({ACQ_GRID},
                              q0.options().dtype(torch::kInt32));
@@ -1408,6 +1685,42 @@ void acq_select(torch::Tensor q0, torch::Tensor h0, torch::Tensor active,
                        reinterpret_cast<long long*>(
                            ties.data_ptr<int64_t>()),
                        cap, B);
+    C10_HIP_CHECK(hipGetLastError());
+    if (!want_topk) return;
+
+    auto iopt = q0.options().dtype(torch::kInt32);
+    auto lopt = q0.options().dtype(torch::kInt64);
+    auto ws = torch::empty({TOPK_WS_INTS}, iopt);
+    auto sel = torch::empty({TOPK_MAX}, lopt);
+    auto gbest = torch::empty({grouped ? G : 1}, lopt);
+    int* wsp = ws.data_ptr<int>();
+    auto* selp = reinterpret_cast<unsigned long long*>(
+        sel.data_ptr<int64_t>());
+    auto* gbp = reinterpret_cast<unsigned long long*>(
+        gbest.data_ptr<int64_t>());
+    const float* qp = qbuf.data_ptr<float>();
+    const bool* ap = active.data_ptr<bool>();
+    // survivors: the group winners, or every candidate
+    const unsigned long long* keys = grouped ? gbp : nullptr;
+    const int n = grouped ? G : B;
+    hipLaunchKernelGGL(pairops::topk_prep_kernel, dim3(ACQ_GRID),
+                       dim3(BLOCK), 0, stream.stream(), wsp, gbp,
+                       grouped ? G : 0);
+    if (grouped)
+        hipLaunchKernelGGL(pairops::topk_group_kernel, dim3(ACQ_GRID),
+                           dim3(BLOCK), 0, stream.stream(), qp, ap,
+                           group_of_o->data_ptr<int>(), gbp, G, B);
+    for (int p = 0; p < TOPK_PASSES; ++p)
+        hipLaunchKernelGGL(pairops::topk_hist_kernel, dim3(ACQ_GRID),
+                           dim3(BLOCK), 0, stream.stream(), keys, qp, ap,
+                           wsp, p, K, n);
+    hipLaunchKernelGGL(pairops::topk_gather_kernel, dim3(ACQ_GRID),
+                       dim3(BLOCK), 0, stream.stream(), keys, qp, ap, wsp,
+                       selp, K, n);
+    hipLaunchKernelGGL(pairops::topk_sort_kernel, dim3(1), dim3(TOPK_MAX),
+                       0, stream.stream(), selp, wsp, qp,
+                       reinterpret_cast<long long*>(
+                           topk_o->data_ptr<int64_t>()), K);
     C10_HIP_CHECK(hipGetLastError());
 }
 
@@ -1497,7 +1810,15 @@ void register_pair_ops(pybind11::module_& m) {
           "v3 per-candidate EIG assembly (deterministic) -> (B,)");
     m.def("acq_select", &acq_select,
           "fused acquisition epilogue: qbuf = active ? h0+q0 : -inf; "
-          "out(f64[3]) = [masked max, first argmax, isclose tie count]");
+          "out(f64[3]) = [masked max, first argmax, isclose tie count]; "
+          "topk (K,) int64, when given, = the K best in rank order, one "
+          "per group with group_of, -1 padded",
+          pybind11::arg("q0"), pybind11::arg("h0"),
+          pybind11::arg("active"), pybind11::arg("qbuf"),
+          pybind11::arg("out"), pybind11::arg("ties"),
+          pybind11::arg("topk") = pybind11::none(),
+          pybind11::arg("group_of") = pybind11::none(),
+          pybind11::arg("n_groups") = 0);
     m.def("mfma_probe", &mfma_probe,
           "16x16x32 bf16 MFMA fragment-layout probe");
 }

@@ -445,6 +445,48 @@ def entropy_acquisition(consensus_preds: torch.Tensor) -> torch.Tensor:
     return -(p * torch.log(p + 1e-8)).sum(dim=-1)
 
 
+ACQ_TOPK_MAX = 1024     # slots of the fused epilogue's batch buffer
+
+
+def group_rows(rows: torch.Tensor):
+    """Prediction-pattern groups of a candidate set: (B, H) class rows ->
+    ((B,) int32 index of each row among the unique rows, their number)."""
+    if rows.shape[0] == 0:
+        return torch.zeros(0, dtype=torch.int32, device=rows.device), 0
+    uniq, inv = torch.unique(rows, dim=0, return_inverse=True)
+    return inv.to(torch.int32).contiguous(), int(uniq.shape[0])
+
+
+def acq_topk(q: torch.Tensor, active, group_of, k: int):
+    """The k best candidates in the batch-acquisition order: q descending
+    under float comparison (-0.0 as +0.0, -inf last), then position
+    ascending; with group_of (B,) only each group's first candidate under
+    that order competes. active (B,) bool or None, group_of (B,) integer
+    or None. Returns (positions (m,) int64, values (m,)), m = min(k,
+    competing candidates). The eager twin of acq_select's topk output
+    (the contract is tests/acq_topk_ref.py); NaN is out of scope.
+
+    Two stable sorts, so equal values keep ascending positions:
+    torch.topk promises no order among equal entries."""
+    pos = torch.arange(q.numel(), device=q.device)
+    if active is not None:
+        pos = pos[active]
+    # stable: positions ascend already, so ties stay in position order
+    order = pos[torch.sort(q[pos], descending=True, stable=True).indices]
+    if group_of is not None and order.numel():
+        g = group_of[order].long()
+        # a candidate competes when it is the first of its group in rank
+        # order: stable sort by group, then the run starts
+        by_g = torch.sort(g, stable=True)
+        gs = by_g.values
+        start = torch.ones_like(gs, dtype=torch.bool)
+        start[1:] = gs[1:] != gs[:-1]
+        keep = torch.sort(by_g.indices[start]).values
+        order = order[keep]
+    order = order[:k]
+    return order, q[order]
+
+
 def vma_pairwise(losses: torch.Tensor) -> torch.Tensor:
     """sum_{h'>h} |loss_h - loss_h'| per point via the sorted identity.
 

@@ -66,6 +66,8 @@ def _warm_and_capture(body, read=None):
 
 
 class CODA(ModelSelector):
+    supports_batch = True
+
     def __init__(self, dataset,
                  prefilter_n: int = 0,
                  alpha: float = 0.9,
@@ -604,8 +606,11 @@ class CODA(ModelSelector):
         # values, NaN skipped (tests/acq_ref.py is the contract) - when
         # the tie count is 1 the argmax is unique, and ties go through
         # the seeded host random.choice either way (_acq_result).
+        # A run that asked for a batch also gets the (1024,) rank-ordered
+        # slots (acq.topk_args(); empty otherwise - today's three kernels)
         ops._ext.acq_select(q0.contiguous(), H0.reshape(1).contiguous(),
-                            acq.active, acq.qbuf, acq.out, acq.ties)
+                            acq.active, acq.qbuf, acq.out, acq.ties,
+                            *acq.topk_args())
 
     def _acq_result(self):
         idx, q, tied = self._pair_acq.result()
@@ -620,14 +625,15 @@ class CODA(ModelSelector):
                          and len(self._active_candidates)
                          > self.prefilter_n))
 
-    def _graphed_acquire(self):
+    def _graphed_acquire(self, read=None):
+        read = read or self._acq_result
         if self._acq_graph is None:
             self._sync_pair_cache()    # outside the capture
             self._acq_graph, first = _warm_and_capture(self._acq_body,
-                                                       self._acq_result)
+                                                       read)
             return first
         self._acq_graph.replay()
-        return self._acq_result()
+        return read()
 
     # ------------------------------------------------------------------
     def get_next_item_to_label(self):
@@ -679,6 +685,76 @@ class CODA(ModelSelector):
             self.stochastic = True
             return cand[idx_local], float(q_vals[idx_local])
         return cand[int(bi)], bv
+
+    # -- batch acquisition ---------------------------------------------
+    def get_next_items_to_label(self, k, distinct: bool = True):
+        """The k best unlabeled points to label next, best first, as
+        [(point id, q value)]; fewer when fewer candidates compete.
+
+        k == 1 is get_next_item_to_label(), wrapped: the seeded isclose
+        tie-break, its RNG draws and the `stochastic` flag are the
+        single-pick path's. k > 1 is deterministic: q descending, then
+        position (= point id) ascending, so equal EIG values - the norm
+        early in a run - need no draw, and neither the RNG nor
+        `stochastic` is touched. With distinct (the default) at most one
+        point per prediction pattern is returned: candidates on which
+        all H models predict the same classes move the posterior the
+        same way for any true class, so the best of each pattern stands
+        for it (ops.reference.acq_topk is the rule; the captured pair
+        path computes it inside the acquisition graph)."""
+        k = int(k)
+        if not 1 <= k <= ops.ACQ_TOPK_MAX:
+            raise ValueError(f"k must lie in [1, {ops.ACQ_TOPK_MAX}], "
+                             f"got {k}")
+        if k == 1:
+            return [self.get_next_item_to_label()]
+        if self.q != "eig":
+            raise NotImplementedError(self.q)
+        if distinct and self.comm.is_distributed and not self._replicated:
+            raise ValueError(
+                "this process holds a shard of the model axis, so it "
+                "cannot see prediction patterns: pass distinct=False")
+        distinct = bool(distinct)
+        acq = self._pair_acq
+        if self._use_label_graph and self._acq_eligible():
+            # the captured acquisition writes the batch itself. Whether
+            # it does, and per pattern or not, is a capture-time choice
+            # (k is not: the kernel fills all 1024 slots)
+            if acq.enable_topk(distinct):
+                self._drop_graphs()
+            pending, self._acq_pending = self._acq_pending, None
+
+            def read():
+                return acq.result_topk(k)
+
+            if pending is not None:
+                # computed during add_label. The first label's warm-up
+                # decoded its single pick to the host; the slots wait in
+                # the device buffer either way (a capture records, it
+                # does not run)
+                return read()
+            if self._label_graph is not None:
+                return self._graphed_acquire(read)
+        else:
+            self._acq_pending = None
+        # eager: CPU, the table engine, prefiltered subsets, distributed
+        # ranks (every rank ranks the same gathered scores, so they agree
+        # without a collective)
+        q_vals, cand = self.eig_batched()
+        cand = list(cand)
+        group_of = None
+        if distinct:
+            group_of, _ = ops.group_rows(self._global_classes(
+                torch.tensor(cand, dtype=torch.long, device=self.device)))
+        pos, vals = ops.acq_topk(q_vals, None, group_of, k)
+        return [(cand[p], v) for p, v in zip(pos.tolist(), vals.tolist())]
+
+    def add_labels(self, idxs, classes, probs):
+        """add_label for each of a batch's answers, in order. On the
+        captured path each label still runs an acquisition (one merged
+        graph), of which only the round's last is read."""
+        for idx, y, p in zip(idxs, classes, probs):
+            self.add_label(idx, y, p)
 
     # -- label update --------------------------------------------------
     def _posterior_update(self, y_t, col):

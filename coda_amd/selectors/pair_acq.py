@@ -16,6 +16,7 @@ import struct
 import torch
 
 from ..ops import pair as pops
+from ..ops.reference import ACQ_TOPK_MAX, group_rows
 from ..util import pair_cache_fits
 
 
@@ -67,6 +68,61 @@ class PairAcquisition:
                                         pin_memory=True)
             self.ties_host = torch.empty(8192, dtype=torch.int64,
                                          pin_memory=True)
+
+        # batch acquisition (allocated by enable_topk on the first batch
+        # request; a run that never asks for one holds none of it): the
+        # prediction-pattern groups, the (1024,) slot buffer acq_select
+        # fills in rank order, and its pinned mirror. topk_distinct is
+        # what the captured graph was given: None = no batch outputs.
+        self.group_of, self.n_groups = None, 0
+        self.topk = self.topk_host = None
+        self.topk_distinct = None
+
+    # -- batch acquisition ---------------------------------------------
+    def groups(self):
+        """(group_of (B,) int32, n_groups): the index of each candidate's
+        row among the unique rows of the (B, H) class matrix. Static, so
+        built once, outside any capture."""
+        if self.group_of is None:
+            self.group_of, self.n_groups = group_rows(self.cls_rows)
+        return self.group_of, self.n_groups
+
+    def enable_topk(self, distinct: bool) -> bool:
+        """Have the captured acquisition write batch outputs, one per
+        group when distinct. True when that changes what a capture must
+        contain (the caller drops its graphs)."""
+        if self.topk is None:
+            dev = self.active.device
+            self.topk = torch.full((ACQ_TOPK_MAX,), -1, dtype=torch.int64,
+                                   device=dev)
+            self.topk_host = torch.empty(ACQ_TOPK_MAX, dtype=torch.int64,
+                                         pin_memory=True)
+        if distinct:
+            self.groups()
+        changed = self.topk_distinct is not distinct
+        self.topk_distinct = bool(distinct)
+        return changed
+
+    def topk_args(self):
+        """acq_select's trailing arguments for the current choice."""
+        if self.topk_distinct is None:
+            return ()
+        if self.topk_distinct:
+            return (self.topk, self.group_of, self.n_groups)
+        return (self.topk,)
+
+    def result_topk(self, k: int):
+        """[(point id, q value)] of the first k filled slots of the batch
+        last written; one D2H copy of k words."""
+        th = self.topk_host[:k]
+        th.copy_(self.topk[:k])
+        out = []
+        for w in th.tolist():
+            if w == -1:
+                break
+            out.append((self.ids_host[w >> 32], struct.unpack(
+                "<f", struct.pack("<I", w & 0xFFFFFFFF))[0]))
+        return out
 
     def deactivate(self, point_id: int):
         row = self.row_of.get(point_id)

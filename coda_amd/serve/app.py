@@ -11,6 +11,10 @@ page; any HTTP client can drive the loop.
 Endpoints:
     POST /start            reset the session (optional method/params)
     GET  /next             -> {"index": i, "prob": q}
+    GET  /next_batch?k=K   -> {"items": [{"index": i, "prob": q}, ...]}, a
+                           page of up to K points, best first, at most one
+                           per prediction pattern (CODA); each is answered
+                           or skipped through /answer and /skip
     POST /answer           {"index": i, "label": c} -> updated state
     POST /skip             {"index": i}  ("I don't know")
     GET  /pbest            -> P(model is best) vector
@@ -72,6 +76,17 @@ class SelectorSession:
             idx, prob = self.selector.get_next_item_to_label()
             self._pending = int(idx)
             return int(idx), float(prob)
+
+    def next_batch(self, k: int):
+        """A page of up to k items, best first, at most one per
+        prediction pattern; answered or skipped one by one through
+        answer() / skip()."""
+        with self._lock:
+            if not getattr(self.selector, "supports_batch", False):
+                raise NotImplementedError(
+                    f"method '{self.method}' has no batch acquisition")
+            items = self.selector.get_next_items_to_label(int(k))
+            return [(int(i), float(p)) for i, p in items]
 
     def answer(self, index: int, label: int):
         with self._lock:
@@ -194,6 +209,14 @@ def create_app(dataset, method: str = "coda", oracle=None, seed: int = 0,
     def next_item():
         idx, prob = session.next_item()
         return {"index": idx, "prob": prob}
+
+    @app.get("/next_batch")
+    def next_batch(k: int = 8):
+        try:
+            items = session.next_batch(k)
+        except (ValueError, NotImplementedError) as e:
+            raise HTTPException(400, str(e))
+        return {"items": [{"index": i, "prob": p} for i, p in items]}
 
     @app.post("/answer")
     def answer(req: dict = Body(...)):

@@ -117,7 +117,20 @@ def parse_args(argv=None):
                         help="Save selector state every K steps (0 = off); "
                              "an interrupted seed resumes mid-run.")
     parser.add_argument("--checkpoint-dir", default="checkpoints")
-    return parser.parse_args(argv)
+    parser.add_argument("--batch-size", type=int, default=1,
+                        help="Labels per acquisition round. Selectors with "
+                             "batch support (CODA) hand out K points per "
+                             "acquisition, at most one per prediction "
+                             "pattern; the others label K points one by "
+                             "one. The deployed prediction, hence the "
+                             "regret, moves at round ends.")
+    args = parser.parse_args(argv)
+    if not 1 <= args.batch_size <= 1024:
+        parser.error("--batch-size must lie in [1, 1024]")
+    if args.checkpoint_every % args.batch_size:
+        parser.error("--checkpoint-every must be a multiple of "
+                     "--batch-size: checkpoints are written at round ends")
+    return args
 
 
 def build_selector(dataset, args, loss_fn, comm=None):
@@ -202,11 +215,74 @@ def do_model_selection_experiment(dataset, oracle, args, loss_fn, seed=0,
             cumulative_regret_loss = blob["cumulative"]
             random.setstate(blob["py_rng"])
             torch.set_rng_state(blob["torch_rng"])
+            if "regret" in blob:    # batch runs: the regret being held
+                regret_loss = blob["regret"]
             if is_main:
                 print(f"Resumed {ckpt_path} at step {start_m}")
 
-    iterator = tqdm(range(start_m, args.iters)) if is_main \
-        else range(start_m, args.iters)
+    def save_checkpoint(m_done):
+        blob = {"selector": ckpt.state_dict(selector), "m": m_done,
+                "cumulative": cumulative_regret_loss,
+                "regret": float(regret_loss),
+                "py_rng": random.getstate(),
+                "torch_rng": torch.get_rng_state()}
+        path = ckpt_path + (f".rank{comm.rank}" if comm.world > 1 else "")
+        torch.save(blob, path + ".tmp")
+        os.replace(path + ".tmp", path)
+
+    # --batch-size K > 1: rounds of up to K labels (the last may be
+    # shorter, and so is a round whose pool has fewer patterns left); the
+    # deployed prediction is re-read once per round, after its labels
+    K = getattr(args, "batch_size", 1)
+    m = start_m
+    bar = tqdm(total=args.iters, initial=start_m) \
+        if is_main and K > 1 else None
+    while K > 1 and m < args.iters:
+        want = min(K, args.iters - m)
+        t0 = time.perf_counter()
+        if getattr(selector, "supports_batch", False):
+            items = selector.get_next_items_to_label(want)
+            if not items:
+                break               # nothing left to label
+            idxs = [i for i, _ in items]
+            selector.add_labels(idxs, [oracle(i) for i in idxs],
+                                [p for _, p in items])
+            n = len(items)
+        else:
+            for _ in range(want):
+                chosen_idx, selection_prob = \
+                    selector.get_next_item_to_label()
+                selector.add_label(chosen_idx, oracle(chosen_idx),
+                                   selection_prob)
+            n = want
+        best_model_idx_pred = selector.get_best_model_prediction()
+        step_s = (time.perf_counter() - t0) / n
+        new_regret = true_losses[best_model_idx_pred] - best_loss
+        for j in range(1, n + 1):
+            # the labels before the round's last were taken under the
+            # previous round's deployed prediction: its regret is held
+            if j == n:
+                regret_loss = new_regret
+            cumulative_regret_loss += float(regret_loss)
+            if log and is_main and not args.no_mlflow:
+                tracking.log_metric("regret", float(regret_loss),
+                                    step=m + j)
+                tracking.log_metric("cumulative regret",
+                                    float(cumulative_regret_loss),
+                                    step=m + j)
+                tracking.log_metric("step_seconds", step_s, step=m + j)
+        every = args.checkpoint_every
+        if ckpt_path and (m + n) // every > m // every:
+            save_checkpoint(m + n)
+        m += n
+        if bar is not None:
+            bar.update(n)
+    if bar is not None:
+        bar.close()
+
+    # one label per acquisition (the default): the reference loop
+    steps = range(start_m, args.iters) if K == 1 else range(0)
+    iterator = tqdm(steps) if is_main and K == 1 else steps
     for m in iterator:
         t0 = time.perf_counter()
         chosen_idx, selection_prob = selector.get_next_item_to_label()
@@ -302,7 +378,10 @@ def main(argv=None):
     run_name = "-".join([experiment_name, args.method])
     run_id, _, _ = get_run_id(run_name)
     with tracking.start_run(run_id=run_id, run_name=run_name):
-        tracking.log_params(args.__dict__)
+        # batch_size is a run parameter of batch runs only: the default's
+        # rows stay what they were
+        tracking.log_params({k: v for k, v in args.__dict__.items()
+                             if k != "batch_size" or v > 1})
         for seed in range(args.seeds):
             seed_run_name = "-".join([experiment_name, args.method, str(seed)])
             seed_run_id, seed_finished, seed_stochastic = get_run_id(
