@@ -49,6 +49,7 @@
 // contiguous bytes per lane. Layout verified by the mfma_probe test
 // (tests/test_gpu.py).
 
+#include <algorithm>
 #include <climits>
 #include <initializer_list>
 #include <torch/extension.h>
@@ -452,13 +453,20 @@ pair_gemm_entropy128_kernel(const hip_bfloat16* __restrict__ a16,
 // VGPRs and a spill at JT = 17.)
 // y_t == nullptr: block b takes group b (the one-off full build over
 // the full (K, P) operand). Otherwise the class id is read on the
-// device and block b takes group cls_grp_off[y] + b, reading the
-// one-class scratch operand, whose row 0 is structure row run_off[y];
-// the grid is the largest group count of any class, and a block past
-// the class's range returns - the whole block takes that branch, before
-// the first __syncthreads(). Class y's groups cover rows [run_off[y],
-// run_off[y+1]) exactly, so a refresh writes those cache rows and no
-// others.
+// device and block b takes ONE tile: tile b % 4 of group
+// cls_grp_off[y] + b / 4 (a group holds at most 4 tiles; a tile's
+// results do not depend on the grouping, and a refresh has one class's
+// few tiles to spread over the chip, where a block per group ran them
+// back to back behind one B stage), reading the one-class scratch
+// operand, whose row 0 is structure row run_off[y]; the grid is 4x the
+// largest group count of any class, and a block past the class's groups
+// or past its group's tiles returns - the whole block takes that
+// branch, before the first __syncthreads(). Class y's groups cover rows
+// [run_off[y], run_off[y+1]) exactly, so a refresh writes those cache
+// rows and no others.
+#define PBN_GRP_TILES 4   // most tiles of a group: coda_amd/ops/pair.py
+                          // GRP_MAX (tests/test_pair_stream.py ties them)
+
 template <int JT>
 __global__ void __launch_bounds__(BLOCK2)
 pair_gemm_pbn128_kernel(const hip_bfloat16* __restrict__ a16,
@@ -473,19 +481,29 @@ pair_gemm_pbn128_kernel(const hip_bfloat16* __restrict__ a16,
                         float* __restrict__ pm,               // (K, H)
                         float* __restrict__ pinv,             // (K,)
                         int C, int H) {
-    int g = blockIdx.x, a_row0 = 0;
+    int g = blockIdx.x, a_row0 = 0, tsel = -1;
     if (y_t != nullptr) {
         const long long y = y_t[0];
         if (y < 0 || y >= C) return;
-        g += cls_grp_off[y];
+        g = cls_grp_off[y] + (int)(blockIdx.x / PBN_GRP_TILES);
         if (g >= cls_grp_off[y + 1]) return;
+        tsel = (int)(blockIdx.x % PBN_GRP_TILES);
         a_row0 = run_off[y];
     }
     extern __shared__ char smem[];
     const int twoH = 2 * H;
     hip_bfloat16* b_lds = reinterpret_cast<hip_bfloat16*>(smem);
 
-    const int t0 = grp_off[g], t1 = grp_off[g + 1];
+    int t0 = grp_off[g];
+    const int t1 = grp_off[g + 1];
+    int tstep = 1;
+    if (tsel >= 0) {
+        // one-class refresh: this block's tile of the group (and every
+        // PBN_GRP_TILES-th after it, should a group ever hold more)
+        t0 += tsel;
+        if (t0 >= t1) return;
+        tstep = PBN_GRP_TILES;
+    }
     const int c = pair_c[t0 * 128];
     const int tid = threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63;
@@ -507,7 +525,7 @@ pair_gemm_pbn128_kernel(const hip_bfloat16* __restrict__ a16,
     }
     __syncthreads();
 
-    for (int tile = t0; tile < t1; ++tile) {
+    for (int tile = t0; tile < t1; tile += tstep) {
     const int k0 = tile * 128;
     f32x4 acc[JT];
 #pragma unroll
@@ -583,15 +601,63 @@ pair_gemm_pbn128_kernel(const hip_bfloat16* __restrict__ a16,
 // ---------------------------------------------------------------------
 // Per-step pass over the pair cache: h_after[k] from pm[k, :], inv[k]
 // and the quantities that move every step (pi_hat, mixture0, one row of
-// pbest_before). Sixteen lanes per pair in the fused kernel's order:
-// lane l walks jt ascending with column j = jt*16 + l (h = j >> 1,
-// v = j & 1), adds the term iff vmask bit h == v, then the same
-// row16_reduce - bit-identical to pair_gemm_entropy128_kernel.
-// A chunk's 16 rows are one contiguous 16*H-float span (runs are
-// 128-padded, so a chunk never straddles classes): staged through LDS
-// with float4 loads, with the class's pbest_before row and mixture0.
+// pbest_before), bit-identical to pair_gemm_entropy128_kernel.
+//
+// The fused kernel gives a pair 16 lanes: lane l walks jt ascending with
+// column j = jt*16 + l (h = j >> 1, v = j & 1) and adds the term iff
+// vmask bit h == v, so lanes 2m and 2m+1 evaluate the SAME term (it
+// depends on h alone) and one of them keeps it. Here a pair has EIGHT
+// lanes: lane m takes h = 8*jt + m, evaluates the term once, and keeps
+// the fused kernel's two running sums - `even` (its lane 2m) and `odd`
+// (lane 2m+1); the vmask bit selects which of them takes the fma, the
+// other keeps its value. odd + even is then row16_reduce's first step,
+// and row8_reduce_last the rest of its tree. Half the transcendental
+// issue, twice the pairs per wave.
+//
+// A block owns one 128-pair tile (one class: runs are 128-padded) as
+// four 32-pair chunks; chunk i+1's rows are in flight in registers while
+// chunk i is evaluated from LDS. A chunk is one contiguous 32*H-float
+// span, loaded as float4 and laid out in LDS with a row stride = 8 mod
+// 64 words, so the 8 pairs of a wave read 64 different banks.
+//
+// Pad rows (run_off / run_live given): a class's run is its base pair,
+// its unique pairs, then padding; a pad row holds the base row's pm and
+// inv bit for bit under an all-zero vmask, so its h_after is the base
+// row's. A chunk with no live row is not read: the block evaluates the
+// class's base row once, through the same code, and stores that value
+// into the chunk's rows. Without the two arguments every chunk is read.
 // ---------------------------------------------------------------------
-#define ECH 4   // 16-pair chunks per block (K % 128 == 0 => K % 64 == 0)
+#define ECH 4        // 32-pair chunks per block: one 128-pair tile
+#define ENQ 5        // float4 per thread per chunk: 8*H/256, H <= 136
+#define EWMAX 5      // vmask words: ceil(136 / 32)
+
+__host__ __device__ __forceinline__ int pair_ent_stride(int H) {
+    return ((H + 55) / 64) * 64 + 8;     // >= H, = 8 mod 64, 16-B rows
+}
+
+// One pair's entropy by the 8 lanes that own it (m = lane & 7), valid in
+// lane m == 7. row: the pair's H selected masses.
+__device__ __forceinline__ float
+pair_ent_row8(const float* row, const float* mix_s, const float* pbb_s,
+              const unsigned (&vw)[EWMAX], float inv, float pic, int m,
+              int H) {
+    float even = 0.f, odd = 0.f;
+#pragma unroll
+    for (int w = 0; w < EWMAX; ++w) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int h = (4 * w + t) * 8 + m;     // h >> 5 == w
+            if (h < H) {
+                const bool bit = (vw[w] >> (h & 31)) & 1;
+                float sel = bit ? odd : even;
+                pair_ent_acc(sel, mix_s[h], pic, row[h], inv, pbb_s[h]);
+                even = bit ? even : sel;
+                odd = bit ? sel : odd;
+            }
+        }
+    }
+    return row8_reduce_last(odd + even);
+}
 
 __global__ void __launch_bounds__(BLOCK)
 pair_entropy_cached_kernel(const float* __restrict__ pm,      // (K, H)
@@ -602,69 +668,115 @@ pair_entropy_cached_kernel(const float* __restrict__ pm,      // (K, H)
                            const float* __restrict__ pi_hat,
                            const float* __restrict__ pbest_before,
                            const float* __restrict__ mixture0,
+                           const int* __restrict__ run_off,   // (C+1,) / null
+                           const int* __restrict__ run_live,  // (C,) / null
                            float* __restrict__ h_after,       // (K,)
                            int H) {
     extern __shared__ char smem[];
-    float* rows = reinterpret_cast<float*>(smem);   // [16 * H]
-    float* mix_s = rows + 16 * H;                   // [H]
+    const int stride = pair_ent_stride(H);
+    float* rows = reinterpret_cast<float*>(smem);   // [32 * stride]
+    float* mix_s = rows + 32 * stride;              // [H]
     float* pbb_s = mix_s + H;                       // [H]
+    float* brow = pbb_s + H;                        // [H] the base row
+    float* bval = brow + H;                         // [1] its entropy
 
-    // the block walks ECH consecutive 16-pair chunks (64 pairs: inside
-    // one 128-pair tile, so one class); chunk i+1's rows are in flight
-    // in registers while chunk i is evaluated from LDS
-    const int kb = blockIdx.x * (16 * ECH);
+    const int kb = blockIdx.x * (32 * ECH);
     const int c = pair_c[kb];
     const int tid = threadIdx.x;
-    const int nv4 = 4 * H;      // float4 per chunk: 16*H floats, <= 544
-    // chunk start kb + 16*ch: (kb + 16*ch)*H*4 bytes, 64-B aligned
+    const int pi = tid >> 3, m = tid & 7;
+    // chunks of this tile that hold a live row (block-uniform)
+    int nlive = ECH, kbase = 0;
+    if (run_live != nullptr) {
+        kbase = run_off[c];
+        const int rem = kbase + run_live[c] - kb;   // live rows from kb on
+        nlive = rem <= 0 ? 0 : (rem >= 32 * ECH ? ECH : (rem + 31) >> 5);
+    }
+
+    const int nv4 = 8 * H;      // float4 per chunk: 32*H floats, <= 1088
+    // chunk start kb + 32*ch: (kb + 32*ch)*H*4 bytes, 128-B aligned
     const f32x4* g = reinterpret_cast<const f32x4*>(pm + (size_t)kb * H);
     // (native vectors: an array of HIP's float4 struct stays in scratch)
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    f32x4 nxt[3];
+    f32x4 nxt[ENQ];
+    if (nlive > 0) {
 #pragma unroll
-    for (int q = 0; q < 3; ++q)
-        nxt[q] = tid + q * BLOCK < nv4 ? g[tid + q * BLOCK] : zero4;
+        for (int q = 0; q < ENQ; ++q)
+            nxt[q] = tid + q * BLOCK < nv4 ? g[tid + q * BLOCK] : zero4;
+    }
     for (int h = tid; h < H; h += BLOCK) {
         mix_s[h] = mixture0[h];
         pbb_s[h] = pbest_before[(size_t)c * H + h];
+        if (nlive < ECH) brow[h] = pm[(size_t)kbase * H + h];
     }
-    const int pi = tid >> 4, l = tid & 15;
     const float pic = pi_hat[c];
-    const float* row = rows + pi * H;
-    const int twoH = 2 * H;
-    const int JT = (twoH + 15) / 16;
+    // where this thread's float4s land: element 4*(tid + q*BLOCK) of the
+    // chunk is (row, col) = divmod(., H); the same for every chunk
+    int drow[ENQ], dcol[ENQ];
+#pragma unroll
+    for (int q = 0; q < ENQ; ++q) {
+        const int e = 4 * (tid + q * BLOCK);
+        drow[q] = e / H;
+        dcol[q] = e - drow[q] * H;
+    }
 
-#pragma unroll
-    for (int ch = 0; ch < ECH; ++ch) {
-        f32x4* d = reinterpret_cast<f32x4*>(rows);
-#pragma unroll
-        for (int q = 0; q < 3; ++q)
-            if (tid + q * BLOCK < nv4) d[tid + q * BLOCK] = nxt[q];
+    if (nlive < ECH) {
+        // the tile ends in all-pad chunks: the base row's value, once
         __syncthreads();
-        if (ch + 1 < ECH) {
+        if (pi == 0) {
+            unsigned vw[EWMAX];
+#pragma unroll
+            for (int w = 0; w < EWMAX; ++w)
+                vw[w] = w < W ? vmask[(size_t)kbase * W + w] : 0u;
+            const float e = pair_ent_row8(brow, mix_s, pbb_s, vw,
+                                          pinv[kbase], pic, m, H);
+            if (m == 7) bval[0] = e;
+        }
+        __syncthreads();
+        const float e = bval[0];
+        for (int r = nlive * 32 + tid; r < 32 * ECH; r += BLOCK)
+            h_after[kb + r] = e;
+        if (nlive == 0) return;
+    }
+
+#pragma unroll 1
+    for (int ch = 0; ch < nlive; ++ch) {
+        const int k = kb + ch * 32 + pi;
+        unsigned vw[EWMAX];
+#pragma unroll
+        for (int w = 0; w < EWMAX; ++w)
+            vw[w] = w < W ? vmask[(size_t)k * W + w] : 0u;
+        const float inv = pinv[k];
+        if ((H & 3) == 0) {
+#pragma unroll
+            for (int q = 0; q < ENQ; ++q)
+                if (tid + q * BLOCK < nv4)
+                    *reinterpret_cast<f32x4*>(
+                        rows + drow[q] * stride + dcol[q]) = nxt[q];
+        } else {
+            // a float4 may straddle rows
+#pragma unroll
+            for (int q = 0; q < ENQ; ++q)
+                if (tid + q * BLOCK < nv4) {
+                    int r = drow[q], cc = dcol[q];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        while (cc >= H) { cc -= H; ++r; }
+                        rows[r * stride + cc] = nxt[q][i];
+                        ++cc;
+                    }
+                }
+        }
+        __syncthreads();
+        if (ch + 1 < nlive) {
             const f32x4* gn = g + (size_t)(ch + 1) * nv4;
 #pragma unroll
-            for (int q = 0; q < 3; ++q)
+            for (int q = 0; q < ENQ; ++q)
                 nxt[q] = tid + q * BLOCK < nv4 ? gn[tid + q * BLOCK]
                                                : zero4;
         }
-        const int k = kb + ch * 16 + pi;
-        const float inv = pinv[k];
-        float ent = 0.f;
-        unsigned vw = 0u;
-        for (int jt = 0; jt < JT; ++jt) {
-            const int j = jt * 16 + l;
-            // h >> 5 == jt >> 2 for every column of this sweep
-            if ((jt & 3) == 0)
-                vw = (jt >> 2) < W ? vmask[(size_t)k * W + (jt >> 2)] : 0u;
-            if (j >= twoH) continue;
-            const int h = j >> 1, v = j & 1;
-            const int bit = (vw >> (h & 31)) & 1;
-            if (bit == v)
-                pair_ent_acc(ent, mix_s[h], pic, row[h], inv, pbb_s[h]);
-        }
-        const float e = row16_reduce(ent);
-        if (l == 0) h_after[k] = e;
+        const float e = pair_ent_row8(rows + pi * stride, mix_s, pbb_s, vw,
+                                      inv, pic, m, H);
+        if (m == 7) h_after[k] = e;
         __syncthreads();     // rows are overwritten by the next chunk
     }
 }
@@ -810,12 +922,33 @@ pair_entropy_wide_kernel(const hip_bfloat16* __restrict__ m,  // (K, 2H)
 // ---------------------------------------------------------------------
 // Finalize: q[b] = H_before - (1/rowsum) * (arow . h_base
 //                 + sum_{pairs of b} arow[c]*(h_after - h_base[c]))
-// One wave per candidate; fixed reduction order (deterministic).
+// One wave per candidate at a time; fixed reduction order
+// (deterministic): lane l owns classes 4l + 256i, i ascending, then the
+// scalar tail; hits s = off + l + 64i, ascending; wave_reduce_sum.
+//
+// The pass is a stream over the (N, C) `adjusted` rows carrying a
+// gather per hit, so what matters is how many loads a wave has in
+// flight and how few dependent latencies it pays per 4 KB row:
+//   - a strided grid (at most FIN_MAX_BLOCKS blocks) whose waves walk
+//     candidates b, b + stride, ...; h_base (4 KB at C = 1000) is staged
+//     in LDS once per block and serves the row dot and the hit gathers;
+//   - the wave index is made uniform, so cand_ids / cand_off are scalar
+//     loads, and the NEXT candidate's are fetched while this one's row
+//     is in flight;
+//   - per candidate the packed-hit load is issued first, then the row's
+//     float4 chunks four at a time (C = 1000 is one batch), then the
+//     first hit's gathers - all before the first product is formed, and
+//     straight-line, so the compiler's load counters stay exact.
+// Which candidate a wave takes changes nothing in a candidate's sums.
 // ---------------------------------------------------------------------
+#define FIN_MAX_BLOCKS 2048   // 256 CUs x 8 blocks of 4 waves
+#define FIN_LDS_MAX_C 8192    // h_base beyond 32 KB is read from L2
+
+// VEC: C >= 4, the float4 part exists (C < 4 is the scalar tail alone).
+template <bool HB_LDS, bool VEC>
 __global__ void __launch_bounds__(BLOCK)
 pair_eig_finalize_kernel(const float* __restrict__ h_after,   // (K,)
                          const float* __restrict__ h_base,    // (C,)
-                         const int* __restrict__ pair_c,      // (K,)
                          const int* __restrict__ cand_off,    // (B+1,)
                          const long long* __restrict__ cand_ck,  // (hits,)
                          const long* __restrict__ cand_ids,   // (B,)
@@ -823,36 +956,121 @@ pair_eig_finalize_kernel(const float* __restrict__ h_after,   // (K,)
                          const float* __restrict__ row_sums,  // (N,)
                          float H_before,
                          float* __restrict__ q,               // (B,)
-                         int B, int C) {
-    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (b >= B) return;
+                         int B, int C, int nhits) {
+    extern __shared__ char smem[];
+    float* hb_s = reinterpret_cast<float*>(smem);              // [C]
+    if constexpr (HB_LDS) {
+        for (int i = threadIdx.x; i < C; i += BLOCK) hb_s[i] = h_base[i];
+        __syncthreads();       // the only barrier: waves part ways below
+    }
+    auto hb1 = [&](int i) -> float {
+        if constexpr (HB_LDS) return hb_s[i]; else return h_base[i];
+    };
+    auto hb4 = [&](int i) -> f32x4 {
+        if constexpr (HB_LDS)
+            return *reinterpret_cast<const f32x4*>(hb_s + i);
+        else
+            return *reinterpret_cast<const f32x4*>(h_base + i);
+    };
+
     const int lane = threadIdx.x & 63;
-    const long id = cand_ids[b];
-    const float inv = 1.0f / fmaxf(row_sums[id], 1e-12f);
-    const float* arow = adjusted + (size_t)id * C;
-    float base = 0.f;
-    int cc = lane * 4;
-    for (; cc + 3 < C; cc += 256) {   // float4 over the class axis
-        const float4 a = *reinterpret_cast<const float4*>(arow + cc);
-        const float4 hb = *reinterpret_cast<const float4*>(h_base + cc);
-        base += a.x * hb.x + a.y * hb.y + a.z * hb.z + a.w * hb.w;
-    }
-    for (; cc < C; ++cc) base += arow[cc] * h_base[cc];
-    float corr = 0.f;
-    const int s1 = cand_off[b + 1];
-    // (pair, class) packed per hit: one load decodes both, so the
-    // chase is packed -> {h_after, h_base, arow} (2 dependent levels,
-    // the last three loads independent) instead of
-    // cand_pairs -> pair_c -> gathers (3 levels)
-    for (int s = cand_off[b] + lane; s < s1; s += 64) {
-        const long long pk = cand_ck[s];
-        const int k = (int)(pk >> 32);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int stride = gridDim.x * 4;
+    int b = blockIdx.x * 4 + wave;
+    if (b >= B) return;
+    // float4 chunks this lane owns (4*lane + 256*i + 3 < C), and lane
+    // 0's count, the most of any lane
+    const int n4 = C - 3 > 4 * lane ? (C - 3 - 4 * lane + 255) / 256 : 0;
+    const int n4w = C > 3 ? (C - 3 + 255) / 256 : 0;
+    // Every load up to the first product is UNCONDITIONAL, on an address
+    // clamped into bounds: a load under a lane mask costs the compiler
+    // its count of the loads in flight, and it then waits for all of
+    // them at the next use. A clamped load's value is never used.
+    // (global float4 row loads are only 4-B aligned whenever C % 4 != 0,
+    // here as in every row of such a pool: the hardware takes them)
+    const int cvec = C - 4;                    // last in-row float4 start
+    const int cvec_hb = cvec & ~3;             // the same, 16-B aligned (LDS)
+    const int nh1 = nhits - 1;                 // nhits >= 1 (host)
+
+    long id = cand_ids[b];
+    int s0 = cand_off[b], s1 = cand_off[b + 1];
+    for (;;) {
+        const int s = s0 + lane;
+        const bool hit = s < s1;
+        // a lane without a hit gathers entry (pair 0, class 0) - K >= 1
+        // and C >= 1 (host) - whatever the clamped slot holds
+        const long long pk0 = cand_ck[min(hit ? s : s0, nh1)];
+        long long pk = hit ? pk0 : 0;
+        const float rs = row_sums[id];
+        const float* arow = adjusted + (size_t)id * C;
+        // the next candidate's scalars, behind this one's loads
+        const int bn = b + stride;
+        const int bnc = min(bn, B - 1);
+        const long idn = cand_ids[bnc];
+        const int s0n = cand_off[bnc], s1n = cand_off[bnc + 1];
+
+        float base = 0.f;
+        // (native vectors: an array of HIP's float4 stays in scratch)
+        f32x4 a[4], hb[4];
+        if constexpr (VEC) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                a[j] = *reinterpret_cast<const f32x4*>(
+                    arow + min(lane * 4 + j * 256, cvec));
+        }
+        // first hit's gathers
         const int c2 = (int)(pk & 0xffffffff);
-        corr += arow[c2] * (h_after[k] - h_base[c2]);
+        const float ga = arow[c2];
+        const float gh = h_after[(int)(pk >> 32)];
+        const float ghb = hb1(c2);
+        if constexpr (VEC) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                hb[j] = hb4(min(lane * 4 + j * 256, cvec_hb));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                // a select, not a branch: the load must not sink into it
+                const float nb = base
+                    + (a[j][0] * hb[j][0] + a[j][1] * hb[j][1]
+                       + a[j][2] * hb[j][2] + a[j][3] * hb[j][3]);
+                base = j < n4 ? nb : base;
+            }
+            for (int i0 = 4; i0 < n4w; i0 += 4) {      // C > 1024
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    a[j] = *reinterpret_cast<const f32x4*>(
+                        arow + min(lane * 4 + (i0 + j) * 256, cvec));
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    hb[j] = hb4(min(lane * 4 + (i0 + j) * 256, cvec_hb));
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float nb = base
+                        + (a[j][0] * hb[j][0] + a[j][1] * hb[j][1]
+                           + a[j][2] * hb[j][2] + a[j][3] * hb[j][3]);
+                    base = i0 + j < n4 ? nb : base;
+                }
+            }
+        }
+        for (int cc = lane * 4 + n4 * 256; cc < C; ++cc)
+            base += arow[cc] * hb1(cc);
+
+        // (pair, class) packed per hit: one load decodes both, so the
+        // chase is packed -> {h_after, arow} (2 dependent levels)
+        const float c0 = 0.f + ga * (gh - ghb);
+        float corr = hit ? c0 : 0.f;
+        for (int s2 = s + 64; s2 < s1; s2 += 64) {
+            pk = cand_ck[s2];
+            const int k = (int)(pk >> 32);
+            const int cx = (int)(pk & 0xffffffff);
+            corr += arow[cx] * (h_after[k] - hb1(cx));
+        }
+        const float inv = 1.0f / fmaxf(rs, 1e-12f);
+        const float tot = wave_reduce_sum(base + corr);
+        if (lane == 0) q[b] = H_before - tot * inv;
+        if (bn >= B) break;
+        b = bn; id = idn; s0 = s0n; s1 = s1n;
     }
-    (void)pair_c;
-    const float tot = wave_reduce_sum(base + corr);
-    if (lane == 0) q[b] = H_before - tot * inv;
 }
 
 // cls-based wide entropy (H beyond the vmask regime, e.g. 10k-model
@@ -1469,7 +1687,7 @@ void pair_dsum_es_cls(torch::Tensor delta16, torch::Tensor dall,
 
 // y_t absent: all groups from the full (K, P) operand a16.
 // Otherwise class y_t[0]'s groups from the one-class scratch operand
-// (a16 = a_run), on a grid of max_grp blocks.
+// (a16 = a_run), on a grid of 4 * max_grp blocks, one per tile.
 void pair_gemm_pbn(torch::Tensor a16, torch::Tensor egw,
                    torch::Tensor vmask, torch::Tensor pair_c,
                    torch::Tensor grp, torch::Tensor pm,
@@ -1515,7 +1733,7 @@ void pair_gemm_pbn(torch::Tensor a16, torch::Tensor egw,
                     && run_off.numel() == C + 1,
                     "cls_grp_off / run_off must be (C+1,) int32");
         TORCH_CHECK(max_grp >= 1 && max_grp <= nblk);
-        nblk = (int)max_grp;
+        nblk = (int)max_grp * PBN_GRP_TILES;   // one block per tile
         cgo = cls_grp_off.data_ptr<int>();
         roff = run_off.data_ptr<int>();
         yp = reinterpret_cast<const long long*>(y_t.data_ptr<int64_t>());
@@ -1545,12 +1763,18 @@ void pair_gemm_pbn(torch::Tensor a16, torch::Tensor egw,
     else launch(pairops::pair_gemm_pbn128_kernel<17>);
 }
 
+// run_off (C+1,) + run_live (C,) int32, both or neither: class c's rows
+// from run_off[c] + run_live[c] to the end of its run are padding (the
+// base row's pm / inv under an all-zero vmask); tiles' all-pad chunks
+// are then filled from the base row instead of being read.
 torch::Tensor pair_entropy_cached(torch::Tensor pm, torch::Tensor pinv,
                                   torch::Tensor vmask,
                                   torch::Tensor pair_c,
                                   torch::Tensor pi_hat,
                                   torch::Tensor pbest_before,
-                                  torch::Tensor mixture0) {
+                                  torch::Tensor mixture0,
+                                  c10::optional<torch::Tensor> run_off_o,
+                                  c10::optional<torch::Tensor> run_live_o) {
     TORCH_CHECK(pm.is_cuda() && pm.dtype() == torch::kFloat32
                 && pm.is_contiguous() && pm.dim() == 2);
     const int K = pm.size(0);
@@ -1559,16 +1783,35 @@ torch::Tensor pair_entropy_cached(torch::Tensor pm, torch::Tensor pinv,
                 "pair cache covers the fused route only");
     TORCH_CHECK(pinv.is_contiguous() && pinv.numel() == K
                 && pair_c.numel() == K && vmask.size(0) == K);
+    TORCH_CHECK(vmask.is_contiguous() && vmask.size(1) <= EWMAX);
     TORCH_CHECK(mixture0.numel() == H && mixture0.is_contiguous()
                 && pbest_before.is_contiguous()
                 && pbest_before.size(1) == H
                 && pi_hat.is_contiguous());
+    TORCH_CHECK(run_off_o.has_value() == run_live_o.has_value(),
+                "run_off and run_live go together");
+    const int* roff = nullptr;
+    const int* rlive = nullptr;
+    if (run_off_o.has_value()) {
+        const torch::Tensor& run_off = *run_off_o;
+        const torch::Tensor& run_live = *run_live_o;
+        const int64_t C = pbest_before.size(0);
+        TORCH_CHECK(run_off.is_cuda() && run_live.is_cuda()
+                    && run_off.scalar_type() == torch::kInt32
+                    && run_live.scalar_type() == torch::kInt32
+                    && run_off.is_contiguous() && run_live.is_contiguous()
+                    && run_off.numel() == C + 1 && run_live.numel() == C,
+                    "run_off (C+1,) / run_live (C,) must be int32");
+        roff = run_off.data_ptr<int>();
+        rlive = run_live.data_ptr<int>();
+    }
     auto h_after = torch::empty({K}, pi_hat.options());
     if (K == 0) return h_after;
-    const size_t shmem = (size_t)18 * H * sizeof(float);
+    const size_t shmem = ((size_t)32 * pairops::pair_ent_stride(H)
+                          + 3 * H + 1) * sizeof(float);
     auto stream = c10::hip::getCurrentHIPStream();
     hipLaunchKernelGGL(pairops::pair_entropy_cached_kernel,
-                       dim3(K / (16 * ECH)), dim3(BLOCK), shmem,
+                       dim3(K / (32 * ECH)), dim3(BLOCK), shmem,
                        stream.stream(),
                        pm.data_ptr<float>(), pinv.data_ptr<float>(),
                        reinterpret_cast<const unsigned*>(
@@ -1576,7 +1819,7 @@ torch::Tensor pair_entropy_cached(torch::Tensor pm, torch::Tensor pinv,
                        pair_c.data_ptr<int>(), (int)vmask.size(1),
                        pi_hat.data_ptr<float>(),
                        pbest_before.data_ptr<float>(),
-                       mixture0.data_ptr<float>(),
+                       mixture0.data_ptr<float>(), roff, rlive,
                        h_after.data_ptr<float>(), H);
     return h_after;
 }
@@ -1599,18 +1842,43 @@ torch::Tensor pair_eig_finalize(torch::Tensor h_after,
                 && cand_ck.is_contiguous(),
                 "finalize inputs must be contiguous");
     auto q = torch::empty({B}, adjusted.options());
+    if (B == 0) return q;
+    (void)pair_c;   // the packed hit table carries each pair's class
+    TORCH_CHECK(cand_off.numel() == B + 1 && cand_ck.numel() < INT_MAX);
+    // The kernel's first hit load is unconditional, on an index clamped
+    // into the table, and a lane without a hit gathers h_after[0] and
+    // column 0 of its row (values it never uses): both must exist. With
+    // no hit at all the load reads cand_ids' first entry instead (B >= 1
+    // int64, discarded likewise) - nothing is allocated here, so the
+    // call captures.
+    TORCH_CHECK(h_after.numel() >= 1 && C >= 1,
+                "finalize needs at least one pair and one class");
+    const int nhits = cand_ck.numel() ? (int)cand_ck.numel() : 1;
+    const long long* ckp = cand_ck.numel()
+        ? reinterpret_cast<const long long*>(cand_ck.data_ptr<int64_t>())
+        : reinterpret_cast<const long long*>(cand_ids.data_ptr<int64_t>());
     auto stream = c10::hip::getCurrentHIPStream();
-    hipLaunchKernelGGL(pairops::pair_eig_finalize_kernel,
-                       dim3((B + 3) / 4), dim3(BLOCK), 0, stream.stream(),
-                       h_after.data_ptr<float>(),
-                       h_base.data_ptr<float>(), pair_c.data_ptr<int>(),
-                       cand_off.data_ptr<int>(),
-                       reinterpret_cast<const long long*>(
-                           cand_ck.data_ptr<int64_t>()),
-                       cand_ids.data_ptr<long>(),
-                       adjusted.data_ptr<float>(),
-                       row_sums.data_ptr<float>(),
-                       (float)H_before, q.data_ptr<float>(), B, C);
+    const int nblk = std::min((B + 3) / 4, FIN_MAX_BLOCKS);
+    auto launch = [&](auto kern, size_t shmem) {
+        hipLaunchKernelGGL(kern, dim3(nblk), dim3(BLOCK), shmem,
+                           stream.stream(),
+                           h_after.data_ptr<float>(),
+                           h_base.data_ptr<float>(),
+                           cand_off.data_ptr<int>(),
+                           ckp, cand_ids.data_ptr<long>(),
+                           adjusted.data_ptr<float>(),
+                           row_sums.data_ptr<float>(),
+                           (float)H_before, q.data_ptr<float>(), B, C,
+                           nhits);
+    };
+    if (C < 4)
+        launch(pairops::pair_eig_finalize_kernel<true, false>,
+               (size_t)C * sizeof(float));
+    else if (C <= FIN_LDS_MAX_C)
+        launch(pairops::pair_eig_finalize_kernel<true, true>,
+               (size_t)C * sizeof(float));
+    else
+        launch(pairops::pair_eig_finalize_kernel<false, true>, 0);
     return q;
 }
 
@@ -1805,7 +2073,14 @@ void register_pair_ops(pybind11::module_& m) {
           pybind11::arg("max_grp") = 0);
     m.def("pair_entropy_cached", &pair_entropy_cached,
           "per-step entropy pass over the pair cache -> (K,), bit-equal "
-          "to the fused 128-pair kernel");
+          "to the fused 128-pair kernel; run_off + run_live skip the "
+          "all-pad chunks",
+          pybind11::arg("pm"), pybind11::arg("pinv"),
+          pybind11::arg("vmask"), pybind11::arg("pair_c"),
+          pybind11::arg("pi_hat"), pybind11::arg("pbest_before"),
+          pybind11::arg("mixture0"),
+          pybind11::arg("run_off") = pybind11::none(),
+          pybind11::arg("run_live") = pybind11::none());
     m.def("pair_eig_finalize", &pair_eig_finalize,
           "v3 per-candidate EIG assembly (deterministic) -> (B,)");
     m.def("acq_select", &acq_select,

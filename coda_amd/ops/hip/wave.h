@@ -43,3 +43,15 @@ __device__ __forceinline__ float row16_reduce(float v) {
     v = dpp_add<0x118, 0xf>(v);  // row_shr:8 -> lane15 of each row
     return __shfl(v, 15, 16);    // broadcast row total to all 16 lanes
 }
+
+// Sum over each aligned group of 8 lanes, valid in the group's LAST lane
+// only. With v[m] = x[2m+1] + x[2m] this is row16_reduce's tree over the
+// 16 values x, level for level: its first row_shr:1 step forms exactly
+// those pair sums in the odd lanes, and the last lane of a group reads
+// nothing from outside the group.
+__device__ __forceinline__ float row8_reduce_last(float v) {
+    v = dpp_add<0x111, 0xf>(v);  // row_shr:1
+    v = dpp_add<0x112, 0xf>(v);  // row_shr:2
+    v = dpp_add<0x114, 0xf>(v);  // row_shr:4 -> lanes 7 and 15 of each row
+    return v;
+}

@@ -59,6 +59,12 @@ def tile_for(H: int, B: int) -> int:
     return 128 if B >= 4096 else PAIR_TILE
 
 
+# Most 128-pair tiles in one tile group. The one-class cache refresh
+# launches this many blocks per group, one tile each: pair.hip's
+# PBN_GRP_TILES (tests/test_pair_stream.py holds the two together).
+GRP_MAX = 4
+
+
 class PairStructure(NamedTuple):
     """Static hit structure for a fixed candidate set.
 
@@ -108,6 +114,10 @@ class PairStructure(NamedTuple):
     run_off: torch.Tensor = None
     max_grp: int = 0         # most tile groups of any class
     max_run: int = 0         # longest class run, in pairs
+    # (C,) int32 — live rows of class c's run: its base pair + its unique
+    # pairs; rows [run_off[c] + run_live[c], run_off[c+1]) are padding,
+    # which the cached entropy pass fills from the base row unread
+    run_live: torch.Tensor = None
 
     @property
     def K(self) -> int:
@@ -267,7 +277,6 @@ def build_pairs(cls_rows: torch.Tensor, cand_ids: torch.Tensor,
     # WRONG candidates' rows (caught by the GPU loopback world-4 test)
     grp_off = None
     if tile == 128 and K % 128 == 0 and K > 0:
-        GRP_MAX = 4
         tc = pair_c[::128]                         # (T,) tile classes
         T = tc.numel()
         newc = torch.ones(T, dtype=torch.bool, device=device)
@@ -288,7 +297,8 @@ def build_pairs(cls_rows: torch.Tensor, cand_ids: torch.Tensor,
         per_class = dict(cls_grp_off=cls_grp_off,
                          run_off=run_off.to(torch.int32),
                          max_grp=int(grp_per_cls.max()),
-                         max_run=int(run_len.max()))
+                         max_run=int(run_len.max()),
+                         run_live=(class_counts + 1).to(torch.int32))
     else:
         per_class = {}
 
@@ -488,7 +498,8 @@ def pair_cache_h_after(cache: PairCache, ps: PairStructure,
     import coda_amd.ops as O
     return O._ext.pair_entropy_cached(
         cache.pm, cache.pinv, ps.vmask, ps.pair_c, pi_hat.contiguous(),
-        pbest_before.contiguous(), mixture0.contiguous())
+        pbest_before.contiguous(), mixture0.contiguous(),
+        ps.run_off, ps.run_live)
 
 
 def eig_from_pairs(h_after: torch.Tensor, ps: PairStructure,

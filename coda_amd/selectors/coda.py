@@ -253,6 +253,12 @@ class CODA(ModelSelector):
         self._label_graph = None
         self._acq_graph = None
         self._acq_pending = None
+        # the merged graph's mixture0 (= the marginal P(best) get_pbest
+        # returns) with the posterior version it belongs to;
+        # _acq_mixture: the tensor the last run or recording of
+        # _acq_body produced, _label_mixture: the label graph's own
+        self._mixture_cache = (-1, None)
+        self._acq_mixture = self._label_mixture = None
 
     def _gather_global_betas(self):
         """Replicated global (H, C) diagonal-Beta view (gathered here;
@@ -590,6 +596,9 @@ class CODA(ModelSelector):
         acq = self._pair_acq
         rows, pi = self._g_rows, self._g_pi
         mixture0, H0 = ops.mixture_entropy(rows, pi)
+        # kept for get_pbest(); holding it also keeps a capture from
+        # handing its block to a later tensor of the same graph
+        self._acq_mixture = mixture0
         # cached: one streaming pass over the cache (kept current by
         # _graph_label_update's one-class refresh)
         h_after = None if acq.cache is None else pops.pair_cache_h_after(
@@ -855,8 +864,17 @@ class CODA(ModelSelector):
             # the capture, serves the next get_next
             self._label_graph, pending = _warm_and_capture(
                 body, self._acq_result if self._merged_acq else None)
+            # the capture rebound it to the graph's buffer, which the
+            # first replay fills: nothing to serve for this label
+            self._label_mixture = (self._acq_mixture if self._merged_acq
+                                   else None)
         else:
             self._label_graph.replay()
+            if self._label_mixture is not None:
+                # the replay's acquisition half computed the mixture of
+                # the rows and pi_hat it has just updated
+                self._mixture_cache = (self._posterior_version + 1,
+                                       self._label_mixture)
         self.pi_hat = self._g_pi
         self._pi_xi_cache = None
         self._pbest_rows_cache = (self._posterior_version + 1,
@@ -924,6 +942,7 @@ class CODA(ModelSelector):
         An acquisition computed before that may select it: a pending
         result is dropped here, for every caller."""
         self._acq_pending = None
+        self._mixture_cache = (-1, None)
         try:
             self._active_candidates.remove(idx)
         except ValueError:
@@ -942,10 +961,17 @@ class CODA(ModelSelector):
     # ------------------------------------------------------------------
     def get_pbest(self):
         """Marginal P(best) over models (K15): (H,) in GLOBAL model order."""
-        rows = self._pbest_rows_before()     # (C, Hl) / (C, H) replicated
-        # ops.mixture_entropy's column-sum kernel; the torch reduction
-        # over C launches 32 threads (~22 us at C=1000)
-        marg_local = ops.mixture_entropy(rows, self.pi_hat)[0]
+        ver, mix = self._mixture_cache
+        if (mix is not None and ver == self._posterior_version
+                and not self.comm.is_distributed):
+            # the merged label+acquire graph already ran these kernels
+            # on these rows and this pi_hat: same bits, one copy
+            marg_local = mix.clone()
+        else:
+            rows = self._pbest_rows_before()  # (C, Hl) / (C, H) replicated
+            # ops.mixture_entropy's column-sum kernel; the torch
+            # reduction over C launches 32 threads (~22 us at C=1000)
+            marg_local = ops.mixture_entropy(rows, self.pi_hat)[0]
         if self.comm.is_distributed and not self._replicated:
             gathered = self.comm.all_gather_cat(marg_local, dim=0)
             pbest = gathered[self.comm.unshard_order(self.H).to(gathered.device)]
